@@ -29,9 +29,19 @@ order).  After the W requested warm-up steps the bench keeps stepping, untimed, 
 ``--prewarm-s`` seconds (default 0.5) of warm-up have passed; the JSON line records it.
 
 Rank 0 prints ONE JSON line: value = all ranks' coefficients / max-over-ranks time,
-plus "roofline" (dominant kernel, HIP-event timed on its own stream) and
-"cpu_baseline" (the fp64 oracle restatement of the config's reference path on a
-bounded sample, host cores of this box, N = 1 only).
+plus "roofline" (dominant kernel, HIP-event timed on its own stream).
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds what
+takes work of its own after the timed region: "check" (rank 0's output against the fp64
+oracle), "gather" (the output's copy to host memory, timed) and "cpu_baseline" (the fp64
+oracle restatement of the config's reference path on a bounded sample, host cores of this
+box, N = 1 only); ``--no-gather`` / ``--no-cpu-baseline`` drop one of them again.
+
+``--dump-outputs DIR`` writes what the last timed step left for a caller (Workload.outputs)
+as DIR/<name>.npy, float32 / float64 (complex as a trailing [re, im] axis), at most
+DUMP_BUDGET bytes in all: an output above its share is a fixed, seeded sample of its
+elements.  The inputs are seeded, so two builds run with the same arguments dump
+comparable arrays.
 """
 
 from __future__ import annotations
@@ -198,6 +208,7 @@ class Workload:
     (weak scaling) or rows [lo, hi) of the batch B split over the ranks (strong)."""
     B = 0
     seed = 0
+    out_names: tuple = ()  # file names of outputs()'s tensors under --dump-outputs
 
     def __init__(self, rank, world, dev, scaling):
         import torch
@@ -228,6 +239,7 @@ class C2(Workload):
     name, axis, seed = "c2", "series", 1002
     B, n0, dj, J = 1024, 4096, 1 / 12, 127
     kernel = "cwt_morlet_kernel<12,1,0,0>"
+    out_names = ("w",)
     PER_STEP = {"wtmi::cwt_morlet_kernel<12": 1}  # kernel-name prefix -> launches per step
 
     def setup(self):
@@ -275,6 +287,7 @@ class C5(C2):
     B, n0, dj, J = 65536, 8192, 1 / 24, 255
     chunk = 512
     kernel = "cwt_morlet_kernel<13,1,0,0>"
+    out_names = ("checksum", "w_rows")
 
     def setup(self):
         torch = self.torch
@@ -331,6 +344,7 @@ class C3(Workload):
     B, n, J = 8192, 16384, 10
     kernel = "modwt_vec_kernel<8,4,1024,16>+imodwt_hyb_kernel<8,8,512,2,1024>"
     PER_STEP = {"wtmi::modwt_vec_kernel<": 1, "wtmi::imodwt_hyb_kernel<": 1}
+    out_names = ("coeffs", "xr")
 
     def setup(self):
         from wtmi.wavelets import Wavelet
@@ -373,6 +387,7 @@ class C4(Workload):
     # every wtmi::wct_* kernel of the step once (r03: the normalisation runs inside
     # wct_spectra_plan; no separate moments launches)
     PER_STEP = {"wtmi::wct_": 1}
+    out_names = ("power", "coh", "phase")
 
     def setup(self):
         from wtmi import transforms
@@ -425,6 +440,7 @@ class Stub(Workload):
     name, axis, seed = "stub", "series", 7
     B, n = 10, 256
     kernel = "stub"
+    out_names = ("y",)
 
     def setup(self):
         self.x = self.torch.tensor(synth_rows(self.seed, self.lo, self.hi, self.n), device=self.dev)
@@ -435,6 +451,9 @@ class Stub(Workload):
 
     def step(self):
         self.y = self.torch.fft.rfft(self.x, dim=-1)
+
+    def outputs(self):
+        return [self.y], "complex64 rfft [series, bins]"
 
     def check(self):
         return float(self.x.sum().item())
@@ -574,6 +593,36 @@ def _measure_gather(wl, pageable):
     return rec
 
 
+DUMP_BUDGET = 48 * 1000 * 1000  # bytes of .npy payload per --dump-outputs directory
+
+
+def dump_outputs(wl, out_dir, suffix=""):
+    """Write wl.outputs() as out_dir/<name><suffix>.npy (float32 / float64; a complex tensor as
+    [..., 2] re / im).  Each output has an equal share of DUMP_BUDGET: one that fits is written
+    whole, a larger one as its elements at indices drawn once from a generator seeded by the
+    output's position and element count -- the same indices for the same shape in every run
+    and build."""
+    import torch
+    outs, _ = wl.outputs()
+    assert len(outs) == len(wl.out_names), (len(outs), wl.out_names)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for i, (name, t) in enumerate(zip(wl.out_names, outs)):
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+            raise TypeError(f"output {name}: {t.dtype} is not written by --dump-outputs")
+        keep = DUMP_BUDGET // len(outs) // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng([20240, i, t.numel()]).integers(0, t.numel(), keep))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        written[name + suffix] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return written
+
+
 def pmc_traffic(cfg, per_step):
     """HBM bytes per step of the roofline kernels from the newest committed PMC pass
     (profiles/rNN/pmc_traffic.json, written by scripts/pmc_traffic.py from separate
@@ -681,9 +730,15 @@ def main():
     ap.add_argument("--plan-only", action="store_true",
                     help="print the ranks' row ranges for --gpus / --config / --scaling as JSON "
                          "and exit (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also check rank 0's output against the oracle, "
+                         "time the host gather and run the CPU baseline (a plain run does none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (DUMP_BUDGET bytes "
+                         "at most: a larger output is a fixed seeded sample)")
     ap.add_argument("--cpu-workers", type=int, default=0, help="0 = every usable host core")
     ap.add_argument("--cpu-per-worker", type=int, default=0, help="0 = per-config default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-when", default="after", choices=["before", "after"],
                     help="run the CPU baseline (a child process) before GPU set-up or after the "
                          "timed region: run before, it slowed the timed C2 kernel 5-12 %%")
@@ -698,12 +753,14 @@ def main():
                          "127.0.0.1): the RCCL barrier / all-reduce / gloo side-group gather run on "
                          "one GPU")
     ap.add_argument("--no-gather", action="store_true",
-                    help="skip the host-gather measurement after the timed region")
+                    help="--full without the host-gather measurement")
     ap.add_argument("--rank-timeout", type=float, default=0.0,
                     help="self-launched ranks: wall-clock limit in seconds (0 = none)")
     args = ap.parse_args()
     if args.device == "cpu" and args.config != "stub":
         ap.error("--device cpu runs only --config stub")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.scaling is None:
         args.scaling = DEFAULT_SCALING[args.config]
     if args.plan_only:
@@ -726,7 +783,8 @@ def main():
         workers = args.cpu_workers or info["usable"]
         print(json.dumps(cpu_baseline(args.config, args.cpu_per_worker, workers, info)), flush=True)
         return
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.config != "stub"
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and \
+        args.config != "stub"
     cpu = cpu_baseline_child(args) if want_cpu and args.cpu_baseline_when == "before" else None
 
     import torch
@@ -834,9 +892,12 @@ def main():
     units_all = sharding.sum_over_ranks(float(wl.units))
     own_max, own_min = sharding.max_over_ranks(t_own), -sharding.max_over_ranks(-t_own)
     bar_max, bar_min = sharding.max_over_ranks(t_barrier), -sharding.max_over_ranks(-t_barrier)
-    check = wl.check() if rank == 0 and wl.local else None
+    dumped = None
+    if args.dump_outputs and wl.local:  # before anything below can touch the step's buffers
+        dumped = dump_outputs(wl, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
+    check = wl.check() if args.full and rank == 0 and wl.local else None
     gather_rec = None
-    if args.device == "cuda" and not args.no_gather:
+    if args.full and args.device == "cuda" and not args.no_gather:
         # the pageable comparison only at N = 1 (N ranks' pageable copies would double the host
         # memory the gather holds)
         gather_rec = measure_gather(wl, pageable=world == 1)
@@ -903,6 +964,8 @@ def main():
                               "value uses the max over ranks of own + barrier"},
             "graph": bool(use_graph),
             "gather": gather_rec,
+            "full": args.full,
+            "dump_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if dist_on:

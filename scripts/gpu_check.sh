@@ -20,7 +20,7 @@ for s in $STEPS; do
   case $s in
     smoke) step smoke 400 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
     tests) step pytest_gpu 1500 python -m pytest tests -m gpu -q -rf ${PYTEST_ARGS:-} ; [ $? -le 1 ] || exit 1 ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:-} || exit $? ;;
+    bench) step bench 600 python bench.py --full ${BENCH_ARGS:-} || exit $? ;;
     prof)  step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --no-cpu-baseline ${BENCH_ARGS:-} || exit $?
            python scripts/trace_mean.py $OUT/prof 50 > $OUT/prof/timed_mean.txt; cat $OUT/prof/timed_mean.txt ;;
     traffic)
@@ -40,7 +40,7 @@ for s in $STEPS; do
         step pmc$i 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/pmc$i -o run -- ${PMC_CMD:-python bench.py --steps 3 --warmup 1 --no-cpu-baseline}
         rc=$?; [ $rc -ge 124 ] && exit $rc
       done ;;
-    c3|c4|c5) step bench_$s 600 python bench.py --config $s --steps 5 --warmup 2 --no-cpu-baseline || exit $? ;;
+    c3|c4|c5) step bench_$s 600 python bench.py --full --config $s --steps 5 --warmup 2 --no-cpu-baseline || exit $? ;;
     profcfg) step prof_$PCFG 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$PCFG -o run -- python bench.py --config $PCFG --steps 10 --warmup 3 --no-cpu-baseline || exit $? ;;
     profc3) step profc3 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc3 -o run -- python bench.py --config c3 --steps 10 --warmup 3 --no-cpu-baseline || exit $? ;;
     profall) step profall 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profall -o run -- python scripts/profile_all.py || exit $? ;;

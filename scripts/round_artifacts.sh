@@ -64,7 +64,7 @@ if has bench; then
     ARGS=""
     [ $c = c2 ] && ARGS="--steps 20 --warmup 5"
     [ $c = c2 ] || ARGS="--steps 10 --warmup 3"
-    run bench_$c 600 python bench.py --config $c $ARGS
+    run bench_$c 600 python bench.py --full --config $c $ARGS
     grep '^{' $OUT/bench_$c.log | tail -1 > $OUT/bench_$c.json
     cut -c1-200 $OUT/bench_$c.json
   done

@@ -7,7 +7,8 @@ GPU box) with the conda interpreter that has PyWavelets 1.1.1:
 
 Outputs (small, committed):
   tests/golden/modwt_golden.npz   outputs of the reference's OWN src/modwt.py
-                                   functions (modwt, imodwt, modwtmra, smooth_signal)
+                                   functions (modwt, imodwt, modwtmra, smooth_signal);
+                                   its n = 4096 cases in modwt_golden_4096.npz
   tests/golden/dwt_golden.npz     outputs of PyWavelets 1.1.1 wavedec/waverec and of
                                    the reference's own src/dwt.py helpers
   tests/golden/pywt_filters.json  orthogonal filter banks from PyWavelets 1.1.1
@@ -85,7 +86,11 @@ def make_modwt():
             for lvl, d in sm.items():
                 out[f"c{idx}_smooth{lvl}"] = d["signal"]
     out["ncases"] = np.int64(len(cases))
-    np.savez_compressed(os.path.join(HERE, "modwt_golden.npz"), **out)
+    # two files, each under the 1 MiB limit for a committed file: the n = 4096 cases apart
+    big = {k: v for k, v in out.items() if k != "ncases" and out[k.split("_")[0] + "_x"].size >= 4096}
+    np.savez_compressed(os.path.join(HERE, "modwt_golden_4096.npz"), **big)
+    np.savez_compressed(os.path.join(HERE, "modwt_golden.npz"),
+                        **{k: v for k, v in out.items() if k not in big})
     print("modwt cases", len(cases))
 
 

@@ -131,6 +131,47 @@ def test_force_dist_runs_a_one_rank_group_with_the_gather():
     assert d["config"]["dist_gather"] == [[0.0, 10 * 256.0], [10.0, 10 * 256.0]]
 
 
+def test_dump_outputs_writes_the_last_steps_arrays_the_same_every_run(tmp_path):
+    """--dump-outputs DIR: the step's outputs as DIR/<name>.npy (complex as float32 [.., 2]),
+    equal to the transform of the seeded inputs and identical from run to run; a plain run
+    carries no check (--full adds it)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    for d in ("a", "b"):
+        r, line = _run("--gpus", "1", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert line["dump_outputs"] == {"y": {"shape": [10, 129, 2], "dtype": "float32"}}
+        assert line["full"] is False and line["check"] == {"rank0_sum": None}
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert a.dtype == np.float32 and a.tobytes() == b.tobytes()
+    ref = np.fft.rfft(bench.synth_rows(bench.Stub.seed, 0, 10, 256).astype(np.float64), axis=-1)
+    np.testing.assert_allclose(a[..., 0] + 1j * a[..., 1], ref, rtol=0, atol=1e-4 * np.abs(ref).max())
+    r, line = _run("--gpus", "1", "--full")
+    assert r.returncode == 0 and line["full"] is True and line["check"]["rank0_sum"] is not None
+    assert line["dump_outputs"] is None
+
+
+def test_dump_outputs_samples_a_large_output_within_the_budget(tmp_path, monkeypatch):
+    """An output above its share of DUMP_BUDGET is written as a fixed sample: the same sorted
+    indices in every call, each value the output's own element."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_BUDGET <= 64 * 1000 * 1000
+    wl = bench.Stub(0, 1, torch.device("cpu"), "weak")
+    wl.step()
+    full = torch.view_as_real(wl.y).numpy().reshape(-1, 2)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8 * 100)  # 100 complex64 elements of 1290
+    for d in ("a", "b"):
+        assert bench.dump_outputs(wl, str(tmp_path / d)) == {"y": {"shape": [100, 2], "dtype": "float32"}}
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert a.tobytes() == b.tobytes()
+    idx = np.sort(np.random.default_rng([20240, 0, 1290]).integers(0, 1290, 100))
+    np.testing.assert_array_equal(a, full[idx])
+
+
 @pytest.mark.parametrize("cfg,bound", [("c2", "hbm"), ("c3", "hbm"), ("c4", "valu")])
 def test_roofline_bound_follows_the_committed_profile(cfg, bound):
     """roofline.bound is the larger of the step's HBM fraction and its VALU fraction (the

@@ -99,7 +99,7 @@ def test_bench_two_ranks_gloo_smoke(scaling, glob, per):
     JSON line with n_gpus 2."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c2",
            "--dist-backend", "gloo", "--steps", "3", "--warmup", "1", "--prewarm-s", "0",
-           "--rank-timeout", "240", "--no-cpu-baseline", "--scaling", scaling]
+           "--rank-timeout", "240", "--full", "--no-cpu-baseline", "--scaling", scaling]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -159,7 +159,7 @@ def test_bench_force_dist_rccl():
     barrier and reductions, and the host gather; the JSON line says dist_backend "rccl"."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c2",
            "--force-dist", "--steps", "3", "--warmup", "1", "--prewarm-s", "0",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
@@ -173,6 +173,36 @@ def test_bench_force_dist_rccl():
     assert g["bytes"] == 1024 * 128 * 4096 * 8
     assert g["pinned_ms"] > 0 and g["pinned_ms_max_over_ranks"] == g["pinned_ms"]
     print("gather", {k: g[k] for k in ("pinned_ms", "pinned_GBps", "pageable_ms", "pageable_GBps")})
+
+
+def test_bench_plain_run_dumps_what_the_step_computes(tmp_path):
+    """A plain bench.py run (no --full) carries no check, gather or CPU baseline, and
+    --dump-outputs writes a seeded sample of the last timed step's W (float32 [k, 2], within
+    the 64 MB limit) equal to the same sample of the C2 step run here on the same inputs."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--prewarm-s", "0", "--dump-outputs", str(tmp_path / "run")]
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["full"] is False
+    assert line["cpu_baseline"] is None and line["gather"] is None
+    assert line["check"] == {"rank0_first_last_series_max_row_rel_err_vs_oracle": None}
+    k = bench.DUMP_BUDGET // 8
+    assert line["dump_outputs"] == {"w": {"shape": [k, 2], "dtype": "float32"}}
+    got = np.load(tmp_path / "run" / "w.npy")
+    assert got.dtype == np.float32 and got.nbytes <= 64 * 1000 * 1000
+    wl = bench.C2(0, 1, torch.device("cuda", 0), "weak")
+    wl.step()
+    bench.dump_outputs(wl, str(tmp_path / "here"))
+    want = np.load(tmp_path / "here" / "w.npy")
+    # the same kernel on the same inputs: equal up to fp32 rounding of a reordered sum at most
+    assert np.abs(want).max() > 0
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-6 * np.abs(want).max())
 
 
 def test_pinned_d2h_bitwise_equal_to_pageable():
