@@ -178,6 +178,33 @@ int wtmi_waverec(const float* coeffs, long long batch, long long n, const double
                  const unsigned long long* keep_masks, int n_variants, float* out,
                  long long out_len, void* workspace, void* stream);
 
+/* ---- time-scale regression (K17 / K18) ---------------------------------------------
+ * time_scale_regression (src/regression.py:91-126): wavedec (mode symmetric) of both series,
+ * the level+1 single-array reconstructions of each (reconstruct_signal_component,
+ * src/dwt.py:110-120), OLS of output component on input component per array.
+ * x (input) / y (output): [batch][ld] float32; dec_* / rec_*: HOST pointers to the n_taps filters.
+ * stats: [batch][level+1][8] float64, component k in pywt list order (k = 0: S_J, k: D_{J-k+1}) =
+ *   const, slope, bse_const, bse_slope, rsquared, ssr, nobs, df_resid.
+ *   add_constant != 0: statsmodels OLS of y on [1, x] (df_resid = nobs - 2); else on x alone
+ *   (uncentred rsquared, df_resid = nobs - 1, const = bse_const = 0).  nobs = out_len, pywt's
+ *   waverec length (n for even n and at level 0, n + 1 for odd n): the reference regresses the
+ *   untrimmed components.  The moments are fp64 sums of the fp32 components.
+ *   Degenerate regressor: when the (centred, or without a constant the raw) sum of squares of
+ *   the input component is exactly 0 -- a constant component, e.g. every component of an
+ *   all-zero series -- slope, bse_slope and bse_const are NaN, const = mean(y component)
+ *   (0 without a constant), ssr = the total sum of squares and rsquared = 0.
+ * comps: NULL, or [batch][2][level+1][out_len] float32 (the components themselves; 0 = input series).
+ * n <= 8192 and even n_taps in 2..40 (-2 otherwise: compose wavedec / waverec / wtmi_rows_ols). */
+int wtmi_dwt_tsr(const float* x, const float* y, long long ld, long long batch, long long n,
+                 const double* dec_lo, const double* dec_hi, const double* rec_lo,
+                 const double* rec_hi, int n_taps, int level, int add_constant,
+                 double* stats, float* comps, void* stream);
+/* The same regression of rows that already exist: y row r on x row r, r < rows, both [rows][ld]
+ * float32 with n samples used (MODWT MRA rows, src/modwt.py:197-229; the components of series
+ * longer than 8192 samples).  stats: [rows][8] float64 as above, nobs = n.                  */
+int wtmi_rows_ols(const float* x, const float* y, long long ld, long long rows, long long n,
+                  int add_constant, double* stats, void* stream);
+
 /* ---- per-series moments / affine (K9) -----------------------------------------
  * Replace standardize_series (src/utils/wavelet_helpers.py:22-57) and the
  * covariances of pycwt.ar1 (src/cwt.py:106).  out: [batch][8] float64 =

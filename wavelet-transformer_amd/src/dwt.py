@@ -115,6 +115,27 @@ def wavedec_batch(dwt_data_list: List[DataForDWT]) -> list:
     return out
 
 
+def time_scale_regression_batch(pairs, levels: int, mother_wavelet, add_constant: bool = True
+                                ) -> List[transforms.TimeScaleOLS]:
+    """The fits of the reference's ``time_scale_regression`` (src/regression.py:91-126) for many
+    (input, output) series pairs (engine extension): DWT of both series, the component vectors
+    S_J, D_J .. D_1 and the OLS of output on input component run in ONE fused launch per group
+    of equal-length pairs; one ``TimeScaleOLS`` per pair, in the order given."""
+    out: list = [None] * len(pairs)
+    groups: dict = {}
+    for i, (a, b) in enumerate(pairs):
+        if len(a) != len(b):
+            raise ValueError(f"pair {i}: input and output lengths differ ({len(a)}, {len(b)})")
+        groups.setdefault(len(a), []).append(i)
+    for idx in groups.values():
+        xs = np.stack([np.asarray(pairs[i][0], dtype=np.float64) for i in idx])
+        ys = np.stack([np.asarray(pairs[i][1], dtype=np.float64) for i in idx])
+        fits = transforms.time_scale_regression(xs, ys, levels, mother_wavelet, add_constant)
+        for k, fit in zip(idx, fits):
+            out[k] = fit
+    return out
+
+
 class _ComponentCache:
     """All single-entry reconstructions of one coefficient list, from ONE batched launch.
 

@@ -129,6 +129,25 @@ def time_scale_regression(input_coeffs: npt.NDArray, output_coeffs: npt.NDArray,
     return summary_col(list(fits.values()), stars=True, model_names=list(fits))
 
 
+def time_scale_regression_batch(input_rows: npt.NDArray, output_rows: npt.NDArray,
+                                add_constant: bool = True):
+    """The fits of ``time_scale_regression`` without statsmodels (engine extension): OLS of
+    output row j on input row j for [levels + 1, N] component rows in the order the reference
+    regresses them (row 0 named S_J, then D_J .. D_1), moments and solve in one GPU launch
+    (``wtmi_rows_ols``).  [P, levels + 1, N] stacks of pairs give a list of P results."""
+    import torch
+    x, y = np.asarray(input_rows), np.asarray(output_rows)
+    if x.shape != y.shape or x.ndim not in (2, 3):
+        raise ValueError(f"expected equal [levels + 1, N] or [P, levels + 1, N] rows, got {x.shape} "
+                         f"and {y.shape}")
+    dev = transforms.device()
+    xd = torch.as_tensor(x.reshape(-1, x.shape[-1]), device=dev).to(torch.float32)
+    yd = torch.as_tensor(y.reshape(-1, y.shape[-1]), device=dev).to(torch.float32)
+    stats = transforms.ops.rows_ols(xd, yd, add_constant).cpu().numpy().reshape(-1, x.shape[-2], 8)
+    fits = [transforms.TimeScaleOLS.from_stats(s, add_constant) for s in stats]
+    return fits[0] if x.ndim == 2 else fits
+
+
 def plot_smoothing(smooth_signals: dict, original_t: npt.NDArray, original_y: npt.NDArray,
                    ascending: bool = False, **kwargs):
     """One panel per smoothed signal over the original (src/modwt.py:254-283)."""

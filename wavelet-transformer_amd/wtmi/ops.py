@@ -532,6 +532,79 @@ def waverec(coeffs: torch.Tensor, n: int, rec_lo, rec_hi, level: int,
     return out
 
 
+# ---------------------------------------------------------- time-scale regression
+TSR_MAX_N = 8192   # longest row of the fused kernel (include/wtmi.h: wtmi_dwt_tsr)
+TSR_MAX_TAPS = 40
+STATS = ("const", "slope", "bse_const", "bse_slope", "rsquared", "ssr", "nobs", "df_resid")
+
+
+def _ols_rows(x, y, what):
+    """The operand checks of a regression's row pair (before any device is touched): tensors of
+    equal shape, float32, [n] or [B, n]."""
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be float32 rows, got {t.dtype}")
+    if x.shape != y.shape:
+        raise ValueError(f"{what}: x and y must have the same shape, got {tuple(x.shape)} and "
+                         f"{tuple(y.shape)}")
+    if x.dim() not in (1, 2) or x.shape[-1] < 1:
+        raise ValueError(f"{what}: expected [n] or [batch, n] rows, got shape {tuple(x.shape)}")
+
+
+def rows_ols(x_rows: torch.Tensor, y_rows: torch.Tensor, add_constant: bool = True) -> torch.Tensor:
+    """OLS of y row r on [1, x row r] (or on the x row alone) for float32 [R, n] row pairs:
+    [R, 8] float64 = ``STATS`` (wtmi_rows_ols; nobs = n)."""
+    _ols_rows(x_rows, y_rows, "rows_ols")
+    dev = _check_dev(x_rows, y_rows)
+    x, y = _pair_rows(x_rows, y_rows)
+    R, n = x.shape
+    stats = torch.empty((R, 8), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_rows_ols", _ptr(x), _ptr(y), x.stride(0), R, n, int(bool(add_constant)),
+                  _ptr(stats), _stream(dev))
+    return stats
+
+
+def dwt_time_scale_regression(x: torch.Tensor, y: torch.Tensor, dec_lo, dec_hi, rec_lo, rec_hi,
+                              level: int, *, add_constant: bool = True,
+                              want_components: bool = False):
+    """Per-component OLS of y on x over the DWT components S_J, D_J .. D_1 (pywt list order):
+    {"stats": [B, level + 1, 8] float64 (``STATS``), "components": [B, 2, level + 1, out_len]
+    float32 (0 = x) or None}.  Rows of at most ``TSR_MAX_N`` samples (and even filters of at most
+    ``TSR_MAX_TAPS`` taps) take ONE fused launch; longer ones compose wavedec, waverec with the
+    level + 1 one-bit masks and rows_ols."""
+    _ols_rows(x, y, "dwt_time_scale_regression")
+    if int(level) != level or level < 0:
+        raise ValueError(f"level must be an integer >= 0, got {level!r}")
+    level = int(level)
+    taps = [_taps(a) for a in (dec_lo, dec_hi, rec_lo, rec_hi)]
+    F = taps[0].size
+    if any(t.ndim != 1 or t.size != F for t in taps) or F < 2:
+        raise ValueError("dec_lo, dec_hi, rec_lo and rec_hi must hold the same number of taps "
+                         f"(>= 2), got {[t.shape for t in taps]}")
+    dev = _check_dev(x, y)
+    x, y = _pair_rows(x, y)
+    B, n = x.shape
+    if n > TSR_MAX_N or F % 2 or F > TSR_MAX_TAPS:
+        masks = [1 << k for k in range(level + 1)]
+        comps = torch.stack([waverec(wavedec(r, taps[0], taps[1], level)[0], n, taps[2], taps[3],
+                                     level, masks) for r in (x, y)], dim=1).contiguous()
+        out_len = comps.shape[-1]
+        stats = rows_ols(comps[:, 0].reshape(-1, out_len), comps[:, 1].reshape(-1, out_len),
+                         add_constant).reshape(B, level + 1, 8)
+        return {"stats": stats, "components": comps if want_components else None}
+    out_len = 2 * dwt_lengths(n, F, level)[-1] - F + 2 if level > 0 else n
+    stats = torch.empty((B, level + 1, 8), dtype=torch.float64, device=dev)
+    comps = torch.empty((B, 2, level + 1, out_len), dtype=torch.float32, device=dev) \
+        if want_components else None
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_dwt_tsr", _ptr(x), _ptr(y), x.stride(0), B, n, *(t.ctypes.data_as(VP) for t in taps),
+                  F, level, int(bool(add_constant)), _ptr(stats), _ptr(comps), _stream(dev))
+    return {"stats": stats, "components": comps}
+
+
 # ------------------------------------------------------------ torch custom ops
 # torch.ops.wtmi.* wrappers over the same HIP kernels (CUDA/ROCm dispatch only: a
 # CPU tensor has no kernel and raises).  Filter taps travel as host float64 tensors.
@@ -631,6 +704,26 @@ def _register():
         out_len = 2 * lens[-1] - rec_lo.numel() + 2 if level > 0 else n
         return coeffs.new_empty((coeffs.shape[0] if coeffs.dim() == 2 else 1, out_len),
                                 dtype=torch.float32)
+
+    @lib.custom_op("wtmi::dwt_tsr", mutates_args=())
+    def _dwt_tsr(x: torch.Tensor, y: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor,
+                 rec_lo: torch.Tensor, rec_hi: torch.Tensor, level: int, add_constant: bool
+                 ) -> torch.Tensor:
+        """Per-component OLS statistics of y on x over their DWT components: [B, level + 1, 8]."""
+        banks = [t.cpu().numpy() for t in (dec_lo, dec_hi, rec_lo, rec_hi)]
+        return dwt_time_scale_regression(x, y, *banks, level, add_constant=add_constant)["stats"]
+
+    @_dwt_tsr.register_fake
+    def _(x, y, dec_lo, dec_hi, rec_lo, rec_hi, level, add_constant):
+        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level + 1, 8), dtype=torch.float64)
+
+    @lib.custom_op("wtmi::rows_ols", mutates_args=())
+    def _rows_ols(x: torch.Tensor, y: torch.Tensor, add_constant: bool) -> torch.Tensor:
+        return rows_ols(x, y, add_constant)
+
+    @_rows_ols.register_fake
+    def _(x, y, add_constant):
+        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, 8), dtype=torch.float64)
 
     @lib.custom_op("wtmi::series_stats", mutates_args=())
     def _series_stats(x: torch.Tensor) -> torch.Tensor:

@@ -16,7 +16,8 @@ from __future__ import annotations
 import math
 import os
 import threading
-from typing import Optional
+from dataclasses import dataclass
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -617,6 +618,59 @@ def waverec(coeffs, wavelet, mode="symmetric"):
     if mode != "symmetric":
         raise ValueError("only mode='symmetric' (the reference's) is implemented")
     return waverec_variants(coeffs, wavelet, [(1 << len(coeffs)) - 1])[0]
+
+
+# -------------------------------------------------------- time-scale regression
+@dataclass
+class TimeScaleOLS:
+    """Per-component OLS of an output series on an input series (the fits the reference hands
+    to statsmodels' summary_col, src/regression.py:106-125).  Row c of every array is component
+    ``names[c]``; the columns of params / bse / tvalues / pvalues are (const, slope) with a
+    constant and (slope,) without."""
+
+    names: List[str]
+    params: np.ndarray
+    bse: np.ndarray
+    tvalues: np.ndarray
+    pvalues: np.ndarray
+    rsquared: np.ndarray
+    nobs: int
+    df_resid: int
+
+    @classmethod
+    def from_stats(cls, stats, add_constant: bool = True) -> "TimeScaleOLS":
+        """From one pair's [levels + 1, 8] statistics (``ops.STATS`` columns, pywt list order):
+        t-values and two-sided Student-t p-values are closed forms of the tiny array."""
+        from scipy.special import stdtr
+        s = np.asarray(stats, dtype=np.float64)
+        if s.ndim != 2 or s.shape[1] != 8:
+            raise ValueError(f"stats must be [components, 8], got {s.shape}")
+        levels = s.shape[0] - 1
+        cols = slice(0, 2) if add_constant else slice(1, 2)
+        params, bse = s[:, 0:2][:, cols], s[:, 2:4][:, cols]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            t = params / bse
+        df = s[:, 7:8]
+        return cls([f"S_{levels}"] + [f"D_{levels - j + 1}" for j in range(1, levels + 1)],
+                   params.copy(), bse.copy(), t, 2.0 * stdtr(df, -np.abs(t)), s[:, 4].copy(),
+                   int(s[0, 6]), int(s[0, 7]))
+
+    def stars(self) -> List[List[str]]:
+        """Significance marks of every coefficient, statsmodels summary_col's thresholds:
+        * p < 0.1, ** p < 0.05, *** p < 0.01."""
+        return [["*" * sum(bool(p < a) for a in (0.1, 0.05, 0.01)) for p in row] for row in self.pvalues]
+
+
+def time_scale_regression(input_data, output_data, levels: int, wavelet, add_constant: bool = True):
+    """``time_scale_regression`` of src/regression.py:91-126 on the GPU: DWT of both series, their
+    component vectors S_J, D_J .. D_1 and the OLS of output on input component, one fused launch
+    for a whole batch.  [n] inputs give one ``TimeScaleOLS``, [B, n] inputs a list of B."""
+    w = as_filter_bank(wavelet)
+    x, y = _to_dev(input_data, torch.float32), _to_dev(output_data, torch.float32)
+    res = ops.dwt_time_scale_regression(x, y, w.dec_lo, w.dec_hi, w.rec_lo, w.rec_hi, int(levels),
+                                        add_constant=add_constant)
+    fits = [TimeScaleOLS.from_stats(s, add_constant) for s in _np(res["stats"])]
+    return fits[0] if x.dim() == 1 else fits
 
 
 # ----------------------------------------------------------------------- MODWT
