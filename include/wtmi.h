@@ -205,6 +205,32 @@ int wtmi_dwt_tsr(const float* x, const float* y, long long ld, long long batch, 
 int wtmi_rows_ols(const float* x, const float* y, long long ld, long long rows, long long n,
                   int add_constant, double* stats, void* stream);
 
+/* ---- MODWT multiresolution analysis (K19 / K20) -------------------------------------
+ * wtmi_modwt_mra replaces the MODWT workflow of src/modwt.py:466-487 in one launch: modwt
+ * (:126-144) + modwtmra (:163-194) of x (and of y), smooth_signal (:232-251) and
+ * time_scale_regression on the MRA rows (:197-229).  No coefficient array is formed: level j
+ * applies the autocorrelations of h~ / g~ at dilation 2^(j-1) to the running smooth U_{j-1}.
+ * x / y: [batch][ld] float32, y NULL for single series (P = 1; P = 2 with y, 0 = x).
+ * mra: NULL, or [batch][P][level+1][n] float32, rows [D_1 .. D_J, S_J] (the reference's
+ *   modwtmra(modwt(x)) row order).
+ * smooth: NULL, or [batch][P][level][n]; row l-1 is U_l = smooth_signal(...)[l]["signal"]
+ *   (for an orthonormal bank, as every pywt wavelet of the reference is).
+ * stats: NULL, or [batch][level+1][8] float64 in MRA row order: OLS of y's row on x's row,
+ *   columns, add_constant and the degenerate-regressor rules as wtmi_dwt_tsr, nobs = n.
+ * -1: stats without y, or mra, smooth and stats all NULL.  level in 1..62.
+ * n <= 16384 and n_taps in 2..40 (-2 otherwise: compose wtmi_modwt, one-bit-mask wtmi_imodwt
+ * and wtmi_rows_ols).  A pair holds both series in LDS (2 n floats of the CU's 160 KiB): pairs
+ * of at most 8192 samples run two or more workgroups per CU, longer ones one.              */
+int wtmi_modwt_mra(const float* x, const float* y, long long ld, long long batch, long long n,
+                   const double* dec_lo, const double* dec_hi, int n_taps, int level,
+                   int add_constant, float* mra, float* smooth, double* stats, void* stream);
+/* modwtmra(w, filters) (src/modwt.py:163-194) of coefficient rows that already exist (e.g.
+ * thresholded ones): w and mra [batch][level+1][n] float32, rows [W_1 .. W_J, V_J] in and
+ * [D_1 .. D_J, S_J] out; each row is inverted alone, the zero rows of the reference's masked
+ * inverse are never read.  Limits and return codes as wtmi_modwt_mra.                     */
+int wtmi_modwt_mra_rows(const float* w, long long batch, long long n, const double* dec_lo,
+                        const double* dec_hi, int n_taps, int level, float* mra, void* stream);
+
 /* ---- per-series moments / affine (K9) -----------------------------------------
  * Replace standardize_series (src/utils/wavelet_helpers.py:22-57) and the
  * covariances of pycwt.ar1 (src/cwt.py:106).  out: [batch][8] float64 =

@@ -148,6 +148,29 @@ def time_scale_regression_batch(input_rows: npt.NDArray, output_rows: npt.NDArra
     return fits[0] if x.ndim == 2 else fits
 
 
+def mra(x, filters, level, smooths=False):
+    """modwtmra(modwt(x, filters, level), filters) without the coefficient array, one fused
+    launch (``wtmi_modwt_mra``): rows [D_1 .. D_J, S_J] of a series [N] or of a batch [B, N].
+    smooths=True returns (rows, smooths), smooths[.., l - 1, :] = smooth_signal(...)[l]["signal"].
+    Output dtype follows the input, as ``modwt``."""
+    return transforms.modwt_mra(x, filters, level, smooths=smooths)
+
+
+def modwtmra_batch(w, filters):
+    """``modwtmra`` of coefficient rows [W_1 .. W_J, V_J] that already exist (e.g. thresholded),
+    [J + 1, N] or [B, J + 1, N], in one launch (``wtmi_modwt_mra_rows``)."""
+    return transforms.modwt_mra_rows(w, filters)
+
+
+def time_scale_regression_series(input_series, output_series, levels: int, filters=MOTHER,
+                                 add_constant: bool = True):
+    """The fits of the MODWT workflow (modwt, modwtmra and ``time_scale_regression`` of an input
+    and an output series) from the series themselves in one fused launch: a
+    ``TimeScaleOLS`` ([B, N] inputs: a list) with rows named D_1 .. D_J, S_J."""
+    return transforms.modwt_time_scale_regression(input_series, output_series, levels, filters,
+                                                  add_constant)
+
+
 def plot_smoothing(smooth_signals: dict, original_t: npt.NDArray, original_y: npt.NDArray,
                    ascending: bool = False, **kwargs):
     """One panel per smoothed signal over the original (src/modwt.py:254-283)."""

@@ -605,6 +605,95 @@ def dwt_time_scale_regression(x: torch.Tensor, y: torch.Tensor, dec_lo, dec_hi, 
     return {"stats": stats, "components": comps}
 
 
+# ------------------------------------------------------------------- MODWT MRA
+MRA_MAX_N = 16384   # longest row of the fused kernels (include/wtmi.h: wtmi_modwt_mra)
+MRA_MAX_TAPS = 40
+
+
+def _mra_level(level, what):
+    if int(level) != level or not 1 <= level <= 62:
+        raise ValueError(f"{what}: level must be an integer in 1..62, got {level!r}")
+    return int(level)
+
+
+def _mra_taps(dec_lo, dec_hi, what):
+    lo, hi = _taps(dec_lo), _taps(dec_hi)
+    if lo.ndim != 1 or lo.shape != hi.shape or lo.size < 2:
+        raise ValueError(f"{what}: dec_lo and dec_hi must hold the same number of taps (>= 2), got "
+                         f"{lo.shape} and {hi.shape}")
+    return lo, hi
+
+
+def _masked_rows(w, lo, hi):
+    """[B, J + 1, n] coefficient rows -> MRA rows, one one-bit-mask inverse per row."""
+    return torch.stack([imodwt(w, lo, hi, 1 << j) for j in range(w.shape[1])], dim=1)
+
+
+def modwt_mra(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torch.Tensor] = None,
+              add_constant: bool = True, want_components: bool = True, want_smooths: bool = False):
+    """MODWT multiresolution analysis of float32 rows x ([n] or [B, n]; with y, of the pairs
+    (x, y)): {"components": [B, P, level + 1, n] rows [D_1 .. D_J, S_J] (P = 2 with y, 0 = x),
+    "smooths": [B, P, level, n] (row l - 1 = the reference's smooth_signal key l),
+    "stats": [B, level + 1, 8] float64 (``STATS``; OLS of y's row on x's row, MRA row order)};
+    entries not requested (and stats without y) are None.  Rows of at most ``MRA_MAX_N``
+    samples and filters of at most ``MRA_MAX_TAPS`` taps take ONE fused launch
+    (wtmi_modwt_mra); beyond, modwt, one-bit-mask imodwt, suffix sums and rows_ols compose."""
+    what = "modwt_mra"
+    level = _mra_level(level, what)
+    lo, hi = _mra_taps(dec_lo, dec_hi, what)
+    if y is None:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
+                or x.shape[-1] < 1:
+            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
+        if not (want_components or want_smooths):
+            raise ValueError(f"{what}: no output requested")
+        dev = _check_dev(x)
+        x = _rows(x)
+    else:
+        _ols_rows(x, y, what)
+        dev = _check_dev(x, y)
+        x, y = _pair_rows(x, y)
+    B, n = x.shape
+    P = 1 if y is None else 2
+    if n > MRA_MAX_N or lo.size > MRA_MAX_TAPS:
+        comps = torch.stack([_masked_rows(modwt(r, lo, hi, level), lo, hi)
+                             for r in ((x,) if y is None else (x, y))], dim=1)
+        stats = None if y is None else rows_ols(
+            comps[:, 0].reshape(-1, n), comps[:, 1].reshape(-1, n), add_constant).reshape(B, level + 1, 8)
+        smooths = comps.flip(2).cumsum(2).flip(2)[:, :, 1:].contiguous() if want_smooths else None
+        return {"components": comps if want_components else None, "smooths": smooths, "stats": stats}
+    comps = torch.empty((B, P, level + 1, n), dtype=torch.float32, device=dev) if want_components else None
+    smooths = torch.empty((B, P, level, n), dtype=torch.float32, device=dev) if want_smooths else None
+    stats = torch.empty((B, level + 1, 8), dtype=torch.float64, device=dev) if y is not None else None
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_modwt_mra", _ptr(x), _ptr(y), x.stride(0), B, n, lo.ctypes.data_as(VP),
+                  hi.ctypes.data_as(VP), lo.size, level, int(bool(add_constant)), _ptr(comps),
+                  _ptr(smooths), _ptr(stats), _stream(dev))
+    return {"components": comps, "smooths": smooths, "stats": stats}
+
+
+def modwt_mra_rows(w: torch.Tensor, dec_lo, dec_hi) -> torch.Tensor:
+    """MRA rows [D_1 .. D_J, S_J] of coefficient rows that already exist (the reference's
+    modwtmra(w, filters)): float32 [J + 1, n] or [B, J + 1, n] -> [B, J + 1, n].  One launch
+    (wtmi_modwt_mra_rows) within ``MRA_MAX_N`` / ``MRA_MAX_TAPS``; one-bit-mask imodwt beyond."""
+    what = "modwt_mra_rows"
+    lo, hi = _mra_taps(dec_lo, dec_hi, what)
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() not in (2, 3) \
+            or w.shape[-2] < 2 or w.shape[-1] < 1:
+        raise ValueError(f"{what}: w must be float32 [levels + 1, n] or [batch, levels + 1, n] rows")
+    dev = _check_dev(w)
+    w = (w.unsqueeze(0) if w.dim() == 2 else w).contiguous()
+    B, R, n = w.shape
+    _mra_level(R - 1, what)
+    if n > MRA_MAX_N or lo.size > MRA_MAX_TAPS:
+        return _masked_rows(w, lo, hi)
+    out = torch.empty_like(w)
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_modwt_mra_rows", _ptr(w), B, n, lo.ctypes.data_as(VP), hi.ctypes.data_as(VP),
+                  lo.size, R - 1, _ptr(out), _stream(dev))
+    return out
+
+
 # ------------------------------------------------------------ torch custom ops
 # torch.ops.wtmi.* wrappers over the same HIP kernels (CUDA/ROCm dispatch only: a
 # CPU tensor has no kernel and raises).  Filter taps travel as host float64 tensors.
@@ -724,6 +813,26 @@ def _register():
     @_rows_ols.register_fake
     def _(x, y, add_constant):
         return x.new_empty((x.shape[0] if x.dim() == 2 else 1, 8), dtype=torch.float64)
+
+    @lib.custom_op("wtmi::modwt_mra", mutates_args=())
+    def _modwt_mra(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, level: int
+                   ) -> torch.Tensor:
+        """MRA rows [D_1 .. D_J, S_J] of every series: [B, level + 1, n]."""
+        return modwt_mra(x, dec_lo.cpu().numpy(), dec_hi.cpu().numpy(), level)["components"][:, 0]
+
+    @_modwt_mra.register_fake
+    def _(x, dec_lo, dec_hi, level):
+        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level + 1, x.shape[-1]),
+                           dtype=torch.float32)
+
+    @lib.custom_op("wtmi::modwt_mra_rows", mutates_args=())
+    def _modwt_mra_rows(w: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor) -> torch.Tensor:
+        return modwt_mra_rows(w, dec_lo.cpu().numpy(), dec_hi.cpu().numpy())
+
+    @_modwt_mra_rows.register_fake
+    def _(w, dec_lo, dec_hi):
+        return w.new_empty((w.shape[0] if w.dim() == 3 else 1, w.shape[-2], w.shape[-1]),
+                           dtype=torch.float32)
 
     @lib.custom_op("wtmi::series_stats", mutates_args=())
     def _series_stats(x: torch.Tensor) -> torch.Tensor:

@@ -638,9 +638,10 @@ class TimeScaleOLS:
     df_resid: int
 
     @classmethod
-    def from_stats(cls, stats, add_constant: bool = True) -> "TimeScaleOLS":
+    def from_stats(cls, stats, add_constant: bool = True, names=None) -> "TimeScaleOLS":
         """From one pair's [levels + 1, 8] statistics (``ops.STATS`` columns, pywt list order):
-        t-values and two-sided Student-t p-values are closed forms of the tiny array."""
+        t-values and two-sided Student-t p-values are closed forms of the tiny array.  names:
+        one label per row where the rows are not in pywt list order (MODWT MRA rows)."""
         from scipy.special import stdtr
         s = np.asarray(stats, dtype=np.float64)
         if s.ndim != 2 or s.shape[1] != 8:
@@ -651,8 +652,11 @@ class TimeScaleOLS:
         with np.errstate(invalid="ignore", divide="ignore"):
             t = params / bse
         df = s[:, 7:8]
-        return cls([f"S_{levels}"] + [f"D_{levels - j + 1}" for j in range(1, levels + 1)],
-                   params.copy(), bse.copy(), t, 2.0 * stdtr(df, -np.abs(t)), s[:, 4].copy(),
+        if names is None:
+            names = [f"S_{levels}"] + [f"D_{levels - j + 1}" for j in range(1, levels + 1)]
+        elif len(names) != s.shape[0]:
+            raise ValueError(f"{len(names)} names for {s.shape[0]} components")
+        return cls(list(names), params.copy(), bse.copy(), t, 2.0 * stdtr(df, -np.abs(t)), s[:, 4].copy(),
                    int(s[0, 6]), int(s[0, 7]))
 
     def stars(self) -> List[List[str]]:
@@ -686,3 +690,44 @@ def imodwt(wc, wavelet, keep_mask=None):
     a = np.asarray(wc)
     out = ops.imodwt(_to_dev(a, torch.float32).unsqueeze(0), w.dec_lo, w.dec_hi, keep_mask)
     return _np(out[0], a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+
+
+def _series_dtype(a):
+    return a.dtype if a.dtype in (np.float32, np.float64) else np.float64
+
+
+def modwt_mra(x, wavelet, level, smooths=False):
+    """MODWT multiresolution analysis rows [D_1 .. D_J, S_J] (the reference's
+    modwtmra(modwt(x, ...), ...)) in one fused launch: [n] in gives [level + 1, n], [B, n] in
+    gives [B, level + 1, n].  smooths=True returns (components, smooths) with smooths
+    [.., level, n], row l - 1 = the reference's smooth_signal(...)[l]["signal"]."""
+    w = as_filter_bank(wavelet)
+    a = np.asarray(x)
+    res = ops.modwt_mra(_to_dev(a, torch.float32), w.dec_lo, w.dec_hi, int(level), want_smooths=smooths)
+    out = [_np(res[k][:, 0], _series_dtype(a)) for k in (("components", "smooths") if smooths else ("components",))]
+    out = [o[0] if a.ndim == 1 else o for o in out]
+    return tuple(out) if smooths else out[0]
+
+
+def modwt_mra_rows(wc, wavelet):
+    """The reference's modwtmra(w, filters) of existing rows [W_1 .. W_J, V_J] ([J + 1, n] or
+    [B, J + 1, n]), one launch."""
+    w = as_filter_bank(wavelet)
+    a = np.asarray(wc)
+    out = _np(ops.modwt_mra_rows(_to_dev(a, torch.float32), w.dec_lo, w.dec_hi), _series_dtype(a))
+    return out[0] if a.ndim == 2 else out
+
+
+def modwt_time_scale_regression(x, y, levels: int, wavelet, add_constant: bool = True):
+    """The MODWT workflow's regression (src/modwt.py:197-229 on the modwtmra rows of both
+    series) in one fused launch: [n] inputs give one ``TimeScaleOLS``, [B, n] inputs a list of B.
+    Rows are named for what they hold, D_1 .. D_J, S_J.  (The reference labels rows by position
+    as in its DWT list, so it calls row 0 -- D_1 -- "S_J"; that quirk is not copied.)"""
+    w = as_filter_bank(wavelet)
+    xd, yd = _to_dev(x, torch.float32), _to_dev(y, torch.float32)
+    levels = int(levels)
+    res = ops.modwt_mra(xd, w.dec_lo, w.dec_hi, levels, y=yd, add_constant=add_constant,
+                        want_components=False)
+    names = [f"D_{j}" for j in range(1, levels + 1)] + [f"S_{levels}"]
+    fits = [TimeScaleOLS.from_stats(s, add_constant, names) for s in _np(res["stats"])]
+    return fits[0] if xd.dim() == 1 else fits
