@@ -205,6 +205,26 @@ int wtmi_dwt_tsr(const float* x, const float* y, long long ld, long long batch, 
 int wtmi_rows_ols(const float* x, const float* y, long long ld, long long rows, long long n,
                   int add_constant, double* stats, void* stream);
 
+/* ---- DWT smoothing ladder with per-level OLS (K21) ----------------------------------
+ * ResultsFromDWT.smooth_signal (src/dwt.py:53-73) from the series itself and
+ * wavelet_approximation (src/regression.py:66-88) in one launch.  smooth_l (cD_1 .. cD_l zeroed)
+ * is cA_l pushed through l low-pass-only synthesis steps, so no detail coefficient is computed
+ * and only the low-pass pair of the bank is needed.
+ * x, y: [batch][ld] float32; y may be NULL when stats is NULL.  dec_lo / rec_lo: HOST pointers.
+ * smooth: NULL, or [batch][level][n] float32; row l-1 is smoothed_signal_dict[l]["signal"]
+ *   (already trimmed: n samples, for odd n the first reconstructed sample is dropped).
+ * stats: NULL, or [batch][level][8] float64; row l-1 is the OLS of the raw y on [1, smooth_l(x)],
+ *   or on smooth_l(x) alone when add_constant == 0.  Columns and the degenerate-regressor rule
+ *   exactly as wtmi_dwt_tsr, nobs = n.
+ * -1: both outputs NULL, stats without y, level < 1, ld < n, a NULL bank pointer.
+ * -2: n > 8192, n_taps odd or > 40, level > 60 (compose wtmi_wavedec, wtmi_waverec with the
+ *   level keep-masks and wtmi_rows_ols).  A level deeper than the series supports is exact.
+ * One workgroup per series and group of chains; the chains of a series are split into groups
+ * where their LDS rows exceed half a CU's 160 KiB (csrc/dwt_smooth.hip).                     */
+int wtmi_dwt_smooth(const float* x, const float* y, long long ld, long long batch, long long n,
+                    const double* dec_lo, const double* rec_lo, int n_taps, int level,
+                    int add_constant, float* smooth, double* stats, void* stream);
+
 /* ---- MODWT multiresolution analysis (K19 / K20) -------------------------------------
  * wtmi_modwt_mra replaces the MODWT workflow of src/modwt.py:466-487 in one launch: modwt
  * (:126-144) + modwtmra (:163-194) of x (and of y), smooth_signal (:232-251) and

@@ -5,6 +5,9 @@ Pyramid DWT / inverse DWT (mode 'symmetric') run on the GPU (``wtmi_wavedec`` /
 smoothed signals in ONE batched launch (one variant per level) instead of the
 reference's loop of ``pywt.waverec`` calls (src/dwt.py:53-73).  Coefficient lists
 keep pywt order ``[cA_J, cD_J, ..., cD_1]`` (quirk B.10).
+``smooth_signal_batch`` / ``wavelet_approximation_batch`` compute the same smooths from the
+series themselves, and the OLS of an output series on each, in one fused launch
+(``wtmi_dwt_smooth``: no detail coefficient is formed).
 """
 
 from __future__ import annotations
@@ -131,6 +134,47 @@ def time_scale_regression_batch(pairs, levels: int, mother_wavelet, add_constant
         xs = np.stack([np.asarray(pairs[i][0], dtype=np.float64) for i in idx])
         ys = np.stack([np.asarray(pairs[i][1], dtype=np.float64) for i in idx])
         fits = transforms.time_scale_regression(xs, ys, levels, mother_wavelet, add_constant)
+        for k, fit in zip(idx, fits):
+            out[k] = fit
+    return out
+
+
+def smooth_signal_batch(dwt_data_list: List[DataForDWT]) -> List[Dict[int, Dict[str, npt.NDArray]]]:
+    """The signals of ``run_dwt(d).smooth_signal(d.y_values, d.mother_wavelet)`` for many series
+    (engine extension), straight from the series: per entry the dict {l: {"signal": ...}} for
+    l = levels .. 1 (``levels=None``: pywt's maximum level).  No coefficient list is formed, so
+    the "coeffs" entries of ``smooth_signal`` are not returned.  Entries of one (length, wavelet,
+    level) share ONE fused launch."""
+    out: list = [None] * len(dwt_data_list)
+    groups: dict = {}
+    for i, d in enumerate(dwt_data_list):
+        w = as_filter_bank(d.mother_wavelet)
+        level = d.levels if d.levels is not None else transforms.dwt_max_level(len(d.y_values), w.dec_len)
+        groups.setdefault((len(d.y_values), w.name, tuple(w.dec_lo), level), []).append(i)
+    for (_, _, _, level), idx in groups.items():
+        w = as_filter_bank(dwt_data_list[idx[0]].mother_wavelet)
+        rows = np.stack([np.asarray(dwt_data_list[i].y_values, dtype=np.float64) for i in idx])
+        for k, s in zip(idx, transforms.dwt_smooth(rows, w, level)):
+            out[k] = {lvl: {"signal": s[lvl - 1]} for lvl in range(level, 0, -1)}
+    return out
+
+
+def wavelet_approximation_batch(pairs, levels: int, mother_wavelet, add_constant: bool = True
+                                ) -> List[transforms.TimeScaleOLS]:
+    """The fits of the reference's ``wavelet_approximation`` (src/regression.py:66-88) for many
+    (input, output) series pairs (engine extension): the raw output regressed on each of the
+    ``levels`` smooths of the input, ladder and OLS in ONE fused launch per group of equal-length
+    pairs; one ``TimeScaleOLS`` per pair, in the order given."""
+    out: list = [None] * len(pairs)
+    groups: dict = {}
+    for i, (a, b) in enumerate(pairs):
+        if len(a) != len(b):
+            raise ValueError(f"pair {i}: input and output lengths differ ({len(a)}, {len(b)})")
+        groups.setdefault(len(a), []).append(i)
+    for idx in groups.values():
+        xs = np.stack([np.asarray(pairs[i][0], dtype=np.float64) for i in idx])
+        ys = np.stack([np.asarray(pairs[i][1], dtype=np.float64) for i in idx])
+        fits = transforms.wavelet_approximation(xs, ys, levels, mother_wavelet, add_constant)
         for k, fit in zip(idx, fits):
             out[k] = fit
     return out

@@ -51,6 +51,7 @@ PROTOTYPES = {
     "wtmi_waverec": (_I32, [_P, _I64, _I64, _P, _P, _I32, _I32, _P, _I32, _P, _I64, _P, _P]),
     "wtmi_dwt_tsr": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "wtmi_rows_ols": (_I32, [_P, _P, _I64, _I64, _I64, _I32, _P, _P]),
+    "wtmi_dwt_smooth": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "wtmi_modwt_mra": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "wtmi_modwt_mra_rows": (_I32, [_P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
     "wtmi_series_moments": (_I32, [_P, _I32, _I64, _I64, _I64, _P, _P]),

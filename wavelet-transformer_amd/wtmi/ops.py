@@ -605,6 +605,59 @@ def dwt_time_scale_regression(x: torch.Tensor, y: torch.Tensor, dec_lo, dec_hi, 
     return {"stats": stats, "components": comps}
 
 
+SMOOTH_MAX_LEVEL = 60  # include/wtmi.h: wtmi_dwt_smooth (the fused path shares TSR_MAX_N / TSR_MAX_TAPS)
+
+
+def dwt_smooth(x: torch.Tensor, dec_lo, rec_lo, level: int, *, y: Optional[torch.Tensor] = None,
+               add_constant: bool = True, want_smooth: bool = True):
+    """The DWT smoothing ladder of float32 rows x ([n] or [B, n]) and, with y, the OLS of the raw
+    y on every smooth: {"smooth": [B, level, n] float32 (row l - 1 = the reference's
+    smooth_signal(...)[l]["signal"], trimmed to n samples) or None, "stats": [B, level, 8]
+    float64 (``STATS``, nobs = n) or None without y}.  Rows of at most ``TSR_MAX_N`` samples and
+    even filters of at most ``TSR_MAX_TAPS`` taps take ONE fused launch (wtmi_dwt_smooth), which
+    needs the low-pass pair alone; beyond, wavedec, waverec with the ``level`` keep-masks, the
+    trim and rows_ols compose, with the high-pass pair taken as the quadrature mirror of the
+    low-pass one (dec_hi[k] = (-1)^(k+1) rec_lo[k], rec_hi[k] = (-1)^k dec_lo[k]: every pywt bank)."""
+    what = "dwt_smooth"
+    if int(level) != level or not 1 <= level <= SMOOTH_MAX_LEVEL:
+        raise ValueError(f"{what}: level must be an integer in 1..{SMOOTH_MAX_LEVEL}, got {level!r}")
+    level = int(level)
+    lo_d, lo_r = _taps(dec_lo), _taps(rec_lo)
+    if lo_d.ndim != 1 or lo_d.shape != lo_r.shape or lo_d.size < 2:
+        raise ValueError(f"{what}: dec_lo and rec_lo must hold the same number of taps (>= 2), got "
+                         f"{lo_d.shape} and {lo_r.shape}")
+    if y is None:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
+                or x.shape[-1] < 1:
+            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
+        if not want_smooth:
+            raise ValueError(f"{what}: no output requested")
+        dev = _check_dev(x)
+        x = _rows(x)
+    else:
+        _ols_rows(x, y, what)
+        dev = _check_dev(x, y)
+        x, y = _pair_rows(x, y)
+    B, n = x.shape
+    F = lo_d.size
+    if n > TSR_MAX_N or F % 2 or F > TSR_MAX_TAPS:
+        sign = (-1.0) ** np.arange(F)
+        masks = [(1 << (level + 1 - l)) - 1 for l in range(1, level + 1)]  # drop cD_1 .. cD_l
+        rec = waverec(wavedec(x, lo_d, -sign * lo_r, level)[0], n, lo_r, sign * lo_d, level, masks)
+        smooth = rec[:, :, rec.shape[-1] - n:].contiguous()  # trim_signal: odd n drops sample 0
+        stats = None if y is None else rows_ols(
+            smooth.reshape(-1, n), y[:, None, :].expand(B, level, n).reshape(-1, n),
+            add_constant).reshape(B, level, 8)
+        return {"smooth": smooth if want_smooth else None, "stats": stats}
+    smooth = torch.empty((B, level, n), dtype=torch.float32, device=dev) if want_smooth else None
+    stats = torch.empty((B, level, 8), dtype=torch.float64, device=dev) if y is not None else None
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_dwt_smooth", _ptr(x), _ptr(y), x.stride(0), B, n, lo_d.ctypes.data_as(VP),
+                  lo_r.ctypes.data_as(VP), F, level, int(bool(add_constant)), _ptr(smooth), _ptr(stats),
+                  _stream(dev))
+    return {"smooth": smooth, "stats": stats}
+
+
 # ------------------------------------------------------------------- MODWT MRA
 MRA_MAX_N = 16384   # longest row of the fused kernels (include/wtmi.h: wtmi_modwt_mra)
 MRA_MAX_TAPS = 40
@@ -813,6 +866,16 @@ def _register():
     @_rows_ols.register_fake
     def _(x, y, add_constant):
         return x.new_empty((x.shape[0] if x.dim() == 2 else 1, 8), dtype=torch.float64)
+
+    @lib.custom_op("wtmi::dwt_smooth", mutates_args=())
+    def _dwt_smooth(x: torch.Tensor, dec_lo: torch.Tensor, rec_lo: torch.Tensor, level: int
+                    ) -> torch.Tensor:
+        """The smooths with cD_1 .. cD_l zeroed, l = 1 .. level: [B, level, n]."""
+        return dwt_smooth(x, dec_lo.cpu().numpy(), rec_lo.cpu().numpy(), level)["smooth"]
+
+    @_dwt_smooth.register_fake
+    def _(x, dec_lo, rec_lo, level):
+        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level, x.shape[-1]), dtype=torch.float32)
 
     @lib.custom_op("wtmi::modwt_mra", mutates_args=())
     def _modwt_mra(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, level: int

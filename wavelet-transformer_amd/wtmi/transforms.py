@@ -677,6 +677,32 @@ def time_scale_regression(input_data, output_data, levels: int, wavelet, add_con
     return fits[0] if x.dim() == 1 else fits
 
 
+def dwt_smooth(data, wavelet, level=None):
+    """The signals of ``ResultsFromDWT.smooth_signal`` (src/dwt.py:53-73) from the series itself,
+    one fused launch and no coefficient array: fp64 [level, n] for an [n] series ([B, level, n]
+    for a batch), row l - 1 = smoothed_signal_dict[l]["signal"].  level=None: ``dwt_max_level``."""
+    w = as_filter_bank(wavelet)
+    a = np.asarray(data)
+    if level is None:
+        level = dwt_max_level(a.shape[-1], w.dec_len)
+    out = _np(ops.dwt_smooth(_to_dev(a, torch.float32), w.dec_lo, w.rec_lo, int(level))["smooth"], np.float64)
+    return out[0] if a.ndim == 1 else out
+
+
+def wavelet_approximation(input_data, output_data, levels: int, wavelet, add_constant: bool = True):
+    """``wavelet_approximation`` of src/regression.py:66-88 on the smooths of ``input_data``: the
+    raw output series regressed on each smooth, crystals c = 1 .. levels (the reference dict's
+    key order; row c - 1 is named "S_c" for the detail levels it drops, D_1 .. D_c), ladder and
+    fits in one fused launch.  [n] inputs give one ``TimeScaleOLS``, [B, n] inputs a list of B."""
+    w = as_filter_bank(wavelet)
+    x, y = _to_dev(input_data, torch.float32), _to_dev(output_data, torch.float32)
+    levels = int(levels)
+    res = ops.dwt_smooth(x, w.dec_lo, w.rec_lo, levels, y=y, add_constant=add_constant, want_smooth=False)
+    names = [f"S_{c}" for c in range(1, levels + 1)]
+    fits = [TimeScaleOLS.from_stats(s, add_constant, names) for s in _np(res["stats"])]
+    return fits[0] if x.dim() == 1 else fits
+
+
 # ----------------------------------------------------------------------- MODWT
 def modwt(x, wavelet, level):
     w = as_filter_bank(wavelet)
