@@ -251,6 +251,37 @@ int wtmi_modwt_mra(const float* x, const float* y, long long ld, long long batch
 int wtmi_modwt_mra_rows(const float* w, long long batch, long long n, const double* dec_lo,
                         const double* dec_hi, int n_taps, int level, float* mra, void* stream);
 
+/* ---- MODWT wavelet variance / correlation / cross-correlation (K22) -------------------
+ * The by-scale co-movement table of a MODWT analysis (Percival & Walden ch. 8; Whitcher,
+ * Guttorp & Percival 2000; the lead / lag analysis of Gencay, Selcuk & Whitcher ch. 7) -- the
+ * per-scale counterpart of correlation_matrix_pvalues (src/statistical_analysis.py) -- from the
+ * series themselves in one launch: the coefficients W_j of wtmi_modwt (detail levels 1..level)
+ * are formed in LDS and never written out.
+ * x / y: [batch][ld] float32; y NULL for a single series.  The passes run on x - x[0], y - y[0].
+ * boundary 1 (brick wall, the unbiased estimator): only the coefficients t >= t0 = L_j - 1,
+ *   L_j = (2^j - 1)(n_taps - 1) + 1, which never touch the wrap, count; M_j = n - t0.
+ * boundary 0 (periodic): t0 = 0, M_j = n, lagged indices wrap mod n.
+ * stats: [batch][level][8] float64, row j-1 = var_x, var_y, cov, corr, nobs, ci_lo, ci_hi, n_eff:
+ *   (1/M_j) sums over t >= t0 of W^x W^x, W^y W^y, W^x W^y (no mean subtracted), corr =
+ *   cov / sqrt(var_x var_y), nobs = M_j, ci = tanh(atanh(corr) -+ z / sqrt(n_eff - 3)) with
+ *   n_eff = floor(n / 2^j) - ceil((n_taps - 2)(1 - 2^-j)) (brick wall) or floor(n / 2^j);
+ *   z: the normal quantile of the caller's confidence level.
+ * xcorr: NULL when max_lag == 0, else [batch][level][2 max_lag + 1] float64: column lag + max_lag =
+ *   (1/M_j) sum_t W^x[t] W^y[t + lag] / sqrt(var_x var_y), brick wall: t and t + lag both in
+ *   [t0, n - 1]; periodic: every t, index (t + lag) mod n.  A peak at lag > 0: x leads y.
+ *   Column max_lag is corr itself.
+ * Data-dependent rows (not errors): M_j <= 0: nobs = 0, every other column and the xcorr row NaN;
+ *   var_x or var_y exactly 0 (a constant series): corr, ci and the xcorr row NaN; n_eff <= 3: ci
+ *   NaN; without y only var_x, nobs and n_eff are numbers.
+ * -1: a NULL bank, ld < n, level outside 1..62, boundary not 0 / 1, max_lag < 0 or >= n, stats
+ *   NULL, xcorr without max_lag or max_lag without xcorr, xcorr without y.
+ * -2: n_taps > 40, n > 16384, n > 8192 with max_lag > 0, max_lag > 64 (compose wtmi_modwt and
+ *   reductions over its rows).  One workgroup per pair: two smooth rows and, with lags, two
+ *   coefficient rows of n floats in LDS (128 KiB at n = 8192, one workgroup per CU).        */
+int wtmi_modwt_wcorr(const float* x, const float* y, long long ld, long long batch, long long n,
+                     const double* dec_lo, const double* dec_hi, int n_taps, int level,
+                     int boundary, int max_lag, double z, double* stats, double* xcorr, void* stream);
+
 /* ---- per-series moments / affine (K9) -----------------------------------------
  * Replace standardize_series (src/utils/wavelet_helpers.py:22-57) and the
  * covariances of pycwt.ar1 (src/cwt.py:106).  out: [batch][8] float64 =

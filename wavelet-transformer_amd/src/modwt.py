@@ -171,6 +171,15 @@ def time_scale_regression_series(input_series, output_series, levels: int, filte
                                                   add_constant)
 
 
+def wavelet_correlation_series(input_series, output_series, levels: int, filters=MOTHER, max_lag: int = 0):
+    """How strongly, and with what lead or lag, two series co-move at each MODWT scale (engine
+    extension; the by-scale form of the correlation table): wavelet variance, covariance,
+    correlation with its 95 % interval and the cross-correlation at lags -max_lag .. max_lag of
+    the brick-wall coefficients, from the series themselves in one fused launch
+    (``wtmi_modwt_wcorr``): a ``WaveletCorrelation`` ([B, N] inputs: a list), levels D_1 .. D_J."""
+    return transforms.wavelet_correlation(input_series, output_series, levels, filters, max_lag=max_lag)
+
+
 def plot_smoothing(smooth_signals: dict, original_t: npt.NDArray, original_y: npt.NDArray,
                    ascending: bool = False, **kwargs):
     """One panel per smoothed signal over the original (src/modwt.py:254-283)."""

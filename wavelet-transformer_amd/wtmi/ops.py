@@ -747,6 +747,109 @@ def modwt_mra_rows(w: torch.Tensor, dec_lo, dec_hi) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------- MODWT wavelet variance / correlation
+WCORR_MAX_N = 16384      # longest row of the fused kernel (include/wtmi.h: wtmi_modwt_wcorr)
+WCORR_MAX_LAG_N = 8192   # with max_lag > 0: the coefficient rows share the workgroup's LDS
+WCORR_MAX_LAG = 64
+WCORR_STATS = ("var_x", "var_y", "cov", "corr", "nobs", "ci_lo", "ci_hi", "n_eff")
+WCORR_BOUNDARY = {"periodic": 0, "brickwall": 1}
+
+
+def _wcorr_composed(x, y, lo, hi, level, K, periodic, z):
+    """The numbers of wtmi_modwt_wcorr from modwt coefficient rows and fp64 torch reductions."""
+    B, n = x.shape
+    L = lo.size
+    nan = float("nan")
+    rows = [modwt(r - r[:, :1], lo, hi, level)[:, :level].to(torch.float64) for r in ((x,) if y is None else (x, y))]
+    stats = torch.full((B, level, 8), nan, dtype=torch.float64, device=x.device)
+    xcorr = torch.full((B, level, 2 * K + 1), nan, dtype=torch.float64, device=x.device) if K else None
+    for j in range(1, level + 1):
+        t0 = 0 if periodic else min(n, ((1 << j) - 1) * (L - 1))
+        M = n - t0
+        if M <= 0:
+            stats[:, j - 1, 4] = 0.0
+            continue
+        wx = rows[0][:, j - 1]
+        st = stats[:, j - 1]
+        st[:, 0] = (wx[:, t0:] ** 2).sum(-1) / M
+        st[:, 4] = M
+        neff = (n >> j) - (0 if periodic else (L - 2) - ((L - 2) >> j))
+        st[:, 7] = neff
+        if y is None:
+            continue
+        wy = rows[1][:, j - 1]
+        st[:, 1] = (wy[:, t0:] ** 2).sum(-1) / M
+        st[:, 2] = (wx[:, t0:] * wy[:, t0:]).sum(-1) / M
+        den = torch.sqrt(st[:, 0] * st[:, 1])
+        den = torch.where(den > 0, den, torch.full_like(den, nan))
+        st[:, 3] = st[:, 2] / den
+        if neff > 3:
+            zr, hw = torch.atanh(st[:, 3]), z / float(neff - 3) ** 0.5
+            st[:, 5], st[:, 6] = torch.tanh(zr - hw), torch.tanh(zr + hw)
+        for lag in range(-K, K + 1) if K else ():
+            if lag == 0:
+                s = st[:, 3] * den * M
+            elif periodic:
+                s = (wx * torch.roll(wy, -lag, dims=-1)).sum(-1)
+            else:
+                a, b = max(t0, t0 - lag), min(n, n - lag)
+                s = (wx[:, a:b] * wy[:, a + lag:b + lag]).sum(-1) if b > a else torch.zeros_like(den)
+            xcorr[:, j - 1, lag + K] = st[:, 3] if lag == 0 else s / M / den
+    return stats, xcorr
+
+
+def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torch.Tensor] = None,
+                max_lag: int = 0, boundary: str = "brickwall", ci_level: float = 0.95):
+    """Wavelet variance, covariance and correlation per MODWT detail level of float32 rows x
+    ([n] or [B, n]) and, with y, of the pairs (x, y): {"stats": [B, level, 8] float64
+    (``WCORR_STATS``, row j - 1 = level j), "xcorr": [B, level, 2 max_lag + 1] float64 (column
+    lag + max_lag; a peak at lag > 0: x leads y) or None with max_lag = 0}.  boundary
+    "brickwall" counts only the coefficients clear of the wrap (the unbiased estimator),
+    "periodic" all of them.  Without y only var_x, nobs and n_eff are numbers.  Rows of at most
+    ``WCORR_MAX_N`` samples (``WCORR_MAX_LAG_N`` with lags), ``MRA_MAX_TAPS`` taps and
+    ``WCORR_MAX_LAG`` lags take ONE fused launch (wtmi_modwt_wcorr); beyond, modwt rows and fp64
+    torch reductions compose the same numbers."""
+    from statistics import NormalDist
+    what = "modwt_wcorr"
+    level = _mra_level(level, what)
+    lo, hi = _mra_taps(dec_lo, dec_hi, what)
+    if boundary not in WCORR_BOUNDARY:
+        raise ValueError(f"{what}: boundary must be one of {sorted(WCORR_BOUNDARY)}, got {boundary!r}")
+    if not 0.0 < ci_level < 1.0:
+        raise ValueError(f"{what}: ci_level must lie in (0, 1), got {ci_level!r}")
+    if int(max_lag) != max_lag or max_lag < 0:
+        raise ValueError(f"{what}: max_lag must be an integer >= 0, got {max_lag!r}")
+    K = int(max_lag)
+    if y is None:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
+                or x.shape[-1] < 1:
+            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
+        if K:
+            raise ValueError(f"{what}: max_lag needs a second series y")
+    else:
+        _ols_rows(x, y, what)
+    if K >= x.shape[-1]:
+        raise ValueError(f"{what}: max_lag must be below the series length {x.shape[-1]}, got {K}")
+    z = NormalDist().inv_cdf(0.5 + 0.5 * ci_level)
+    if y is None:
+        dev = _check_dev(x)
+        x = _rows(x)
+    else:
+        dev = _check_dev(x, y)
+        x, y = _pair_rows(x, y)
+    B, n = x.shape
+    if n > (WCORR_MAX_LAG_N if K else WCORR_MAX_N) or lo.size > MRA_MAX_TAPS or K > WCORR_MAX_LAG:
+        stats, xcorr = _wcorr_composed(x, y, lo, hi, level, K, boundary == "periodic", z)
+        return {"stats": stats, "xcorr": xcorr}
+    stats = torch.empty((B, level, 8), dtype=torch.float64, device=dev)
+    xcorr = torch.empty((B, level, 2 * K + 1), dtype=torch.float64, device=dev) if K else None
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_modwt_wcorr", _ptr(x), _ptr(y), x.stride(0), B, n, lo.ctypes.data_as(VP),
+                  hi.ctypes.data_as(VP), lo.size, level, WCORR_BOUNDARY[boundary], K, C.c_double(z),
+                  _ptr(stats), _ptr(xcorr), _stream(dev))
+    return {"stats": stats, "xcorr": xcorr}
+
+
 # ------------------------------------------------------------ torch custom ops
 # torch.ops.wtmi.* wrappers over the same HIP kernels (CUDA/ROCm dispatch only: a
 # CPU tensor has no kernel and raises).  Filter taps travel as host float64 tensors.
@@ -896,6 +999,17 @@ def _register():
     def _(w, dec_lo, dec_hi):
         return w.new_empty((w.shape[0] if w.dim() == 3 else 1, w.shape[-2], w.shape[-1]),
                            dtype=torch.float32)
+
+    @lib.custom_op("wtmi::modwt_wcorr", mutates_args=())
+    def _modwt_wcorr(x: torch.Tensor, y: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor,
+                     level: int, periodic: bool) -> torch.Tensor:
+        """Wavelet variance / covariance / correlation rows (``WCORR_STATS``): [B, level, 8]."""
+        return modwt_wcorr(x, dec_lo.cpu().numpy(), dec_hi.cpu().numpy(), level, y=y,
+                           boundary="periodic" if periodic else "brickwall")["stats"]
+
+    @_modwt_wcorr.register_fake
+    def _(x, y, dec_lo, dec_hi, level, periodic):
+        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level, 8), dtype=torch.float64)
 
     @lib.custom_op("wtmi::series_stats", mutates_args=())
     def _series_stats(x: torch.Tensor) -> torch.Tensor:

@@ -757,3 +757,62 @@ def modwt_time_scale_regression(x, y, levels: int, wavelet, add_constant: bool =
     names = [f"D_{j}" for j in range(1, levels + 1)] + [f"S_{levels}"]
     fits = [TimeScaleOLS.from_stats(s, add_constant, names) for s in _np(res["stats"])]
     return fits[0] if xd.dim() == 1 else fits
+
+
+@dataclass
+class WaveletCorrelation:
+    """Wavelet variance, covariance and correlation of a pair of series per MODWT detail level
+    (``ops.WCORR_STATS``).  Entry j - 1 of every array is level ``names[j - 1]`` = D_j, scale
+    2^(j-1); ci is [levels, 2] (lower, upper); cross_correlation is [levels, len(lags)], column
+    k the correlation of x[t] with y[t + lags[k]] (a peak at a positive lag: x leads y), or None
+    with max_lag = 0.  For a single series (``wavelet_variance``) only variance_x and nobs are
+    numbers."""
+
+    names: List[str]
+    variance_x: np.ndarray
+    variance_y: np.ndarray
+    covariance: np.ndarray
+    correlation: np.ndarray
+    ci: np.ndarray
+    nobs: np.ndarray
+    lags: np.ndarray
+    cross_correlation: Optional[np.ndarray]
+
+    @classmethod
+    def from_stats(cls, stats, xcorr=None) -> "WaveletCorrelation":
+        s = np.asarray(stats, dtype=np.float64)
+        if s.ndim != 2 or s.shape[1] != 8:
+            raise ValueError(f"stats must be [levels, 8], got {s.shape}")
+        K = 0 if xcorr is None else (np.shape(xcorr)[-1] - 1) // 2
+        return cls([f"D_{j}" for j in range(1, s.shape[0] + 1)], s[:, 0].copy(), s[:, 1].copy(), s[:, 2].copy(),
+                   s[:, 3].copy(), s[:, 5:7].copy(), s[:, 4].astype(np.int64), np.arange(-K, K + 1),
+                   None if xcorr is None else np.asarray(xcorr, dtype=np.float64))
+
+    def peak_lags(self) -> np.ndarray:
+        """Per level, the lag at which |cross_correlation| is largest (0 without lags or for an
+        undefined row)."""
+        if self.cross_correlation is None:
+            return np.zeros(len(self.names), dtype=np.int64)
+        return self.lags[np.argmax(np.nan_to_num(np.abs(self.cross_correlation)), axis=1)]
+
+
+def wavelet_correlation(x, y, levels: int, wavelet, max_lag: int = 0, boundary: str = "brickwall",
+                        ci_level: float = 0.95):
+    """Wavelet variance, covariance, correlation (with its ``ci_level`` confidence interval) and
+    lagged cross-correlation of x and y per MODWT scale, one fused launch for a whole batch:
+    [n] inputs give one ``WaveletCorrelation``, [B, n] inputs a list of B."""
+    w = as_filter_bank(wavelet)
+    xd = _to_dev(x, torch.float32)
+    yd = None if y is None else _to_dev(y, torch.float32)
+    res = ops.modwt_wcorr(xd, w.dec_lo, w.dec_hi, int(levels), y=yd, max_lag=max_lag, boundary=boundary,
+                          ci_level=ci_level)
+    st = _np(res["stats"])
+    xc = [None] * len(st) if res["xcorr"] is None else _np(res["xcorr"])
+    out = [WaveletCorrelation.from_stats(s, c) for s, c in zip(st, xc)]
+    return out[0] if xd.dim() == 1 else out
+
+
+def wavelet_variance(x, levels: int, wavelet, boundary: str = "brickwall"):
+    """The wavelet variance of x per MODWT scale (``WaveletCorrelation.variance_x`` and nobs; the
+    pair columns are NaN): [n] in gives one result, [B, n] in a list of B."""
+    return wavelet_correlation(x, None, levels, wavelet, boundary=boundary)
