@@ -206,4 +206,23 @@ inline int launch_status() {
   return e == hipSuccess ? kOk : static_cast<int>(e);
 }
 
+__host__ __device__ __forceinline__ bool aligned16(const void* p) {
+  return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0;
+}
+
+// A launch with more than 64 KiB of dynamic LDS needs the kernel's limit raised first.
+template <typename K>
+inline void allow_lds(K kernel, size_t bytes) {
+  if (bytes > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(bytes));
+}
+
+// Threads of a workgroup whose threads own `per` items each: whole waves, at least one, at most
+// max_threads.  App-sized rows (n ~ 500 .. 1400) get a few waves instead of mostly idle ones.
+inline int threads_for(long long items, int per, int max_threads) {
+  const long long t = ((items + per - 1) / per + kWave - 1) / kWave * kWave;
+  return t < kWave ? kWave : (t > max_threads ? max_threads : static_cast<int>(t));
+}
+
 }  // namespace wtmi

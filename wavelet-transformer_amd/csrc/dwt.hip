@@ -268,13 +268,6 @@ static int waverec_long(const float* coeffs, long long batch, int n, int F, int 
   return kOk;
 }
 
-template <typename K>
-static void allow_dwt_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-}
-
 }  // namespace wtmi
 
 using namespace wtmi;
@@ -308,7 +301,7 @@ extern "C" int wtmi_wavedec(const float* x, long long ld, long long batch, long 
   }
   const int ni = static_cast<int>(n);
   const size_t lds = static_cast<size_t>(2 * (ni + n_taps) + 8) * sizeof(float);
-  allow_dwt_lds(wavedec_kernel, lds);
+  allow_lds(wavedec_kernel, lds);
   hipLaunchKernelGGL(wavedec_kernel, dim3(batch), dim3(kDwtThreads), lds, static_cast<hipStream_t>(stream),
                      x, ld, ni, n_taps, level, fb, coeffs, total);
   return launch_status();
@@ -333,7 +326,7 @@ extern "C" int wtmi_waverec(const float* coeffs, long long batch, long long n, c
   if (n > kDwtMaxN) return kErrUnsupported;  // level 0 of a long series: no transform to invert
   const int cap = static_cast<int>(n) + 2 * n_taps + 8;  // >= any intermediate length
   const size_t lds = static_cast<size_t>(2 * cap) * sizeof(float);
-  allow_dwt_lds(waverec_kernel, lds);
+  allow_lds(waverec_kernel, lds);
   hipLaunchKernelGGL(waverec_kernel, dim3(batch * n_variants), dim3(kDwtThreads), lds,
                      static_cast<hipStream_t>(stream), coeffs, static_cast<int>(n), n_taps, level, fb,
                      keep_masks, n_variants, out, out_len, total, cap);

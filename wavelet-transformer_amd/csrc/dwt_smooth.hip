@@ -42,10 +42,10 @@
 
 namespace wtmi {
 
-constexpr int kSmoothMaxTaps = 40;
+constexpr int kSmoothMaxTaps = kPyrMaxTaps;
 constexpr int kSmoothMaxN = 8192;
 constexpr int kSmoothMaxThreads = 512;
-constexpr int kSmoothMaxLevel = 60;
+constexpr int kSmoothMaxLevel = kPyrMaxLevel;
 constexpr int kSmoothLdsBudget = 79 * 1024;  // bytes of dynamic LDS: two workgroups per CU
 constexpr int kSmoothLdsMax = 159 * 1024;     // (1 KiB each left for the reduction rows)
 
@@ -71,18 +71,6 @@ __device__ __forceinline__ float2 syn_pair(const float* __restrict__ c, int u, c
   return make_float2(ye, yo);
 }
 
-__device__ __forceinline__ void load_row(float* __restrict__ dst, const float* __restrict__ g, int n,
-                                         int tid, int T) {
-  if (aligned16(g)) {
-    const int n4 = n >> 2;
-    for (int i = tid; i < n4; i += T)
-      reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(g)[i];
-    for (int i = 4 * n4 + tid; i < n; i += T) dst[i] = g[i];
-  } else {
-    for (int i = tid; i < n; i += T) dst[i] = g[i];
-  }
-}
-
 // Six waves per SIMD is what the app's shape can hold (n = 1333, db4, J = 7: 39 KB of LDS, four
 // 384-thread workgroups per CU).  Without the bound the scheduler hoists every LDS read of
 // block_sum's thread-0 loop and allocates 116 VGPRs for the whole kernel.
@@ -100,7 +88,7 @@ dwt_smooth_kernel(const float* __restrict__ x, const float* __restrict__ y, long
   float* const X = sm + a.off[0];
 
   // ---- phase A: the approximation pyramid down to level l1 ----
-  load_row(X, x + b * ld, n, tid, T);
+  load_row(X, x + b * ld, n);
   bool prev_small = false;
   for (int j = 1; j <= l1; ++j) {
     float* const cur = sm + a.off[j - 1];
@@ -108,12 +96,7 @@ dwt_smooth_kernel(const float* __restrict__ x, const float* __restrict__ y, long
     const int m = a.len[j - 1], M = a.len[j];
     const bool small = M <= kWave;
     step_sync(prev_small, small);
-    const int lim = small ? kWave : T;
-    if (tid < lim)
-      for (int e = tid; e < 2 * F - 3; e += lim) {  // F - 2 samples before the row, F - 1 after
-        const int idx = e < F - 2 ? e - (F - 2) : m + e - (F - 2);
-        cur[idx] = cur[reflect(idx, m)];
-      }
+    extend_row(cur, m, F, small ? kWave : T);
     step_sync(prev_small, small);
     for (int i = tid; i < M; i += T) {
       const float2* p2 = reinterpret_cast<const float2*>(cur + 2 * i);  // (xe[2i], xe[2i+1])
@@ -158,7 +141,7 @@ dwt_smooth_kernel(const float* __restrict__ x, const float* __restrict__ y, long
   __syncthreads();
   float* const Y = X;  // x is dead once cA_1 exists
   if (STATS) {
-    load_row(Y, y + b * ld, n, tid, T);
+    load_row(Y, y + b * ld, n);
     __syncthreads();
   }
   const int odd = n & 1;  // trim_signal: the first of the n + 1 samples goes
@@ -221,17 +204,14 @@ extern "C" int wtmi_dwt_smooth(const float* x, const float* y, long long ld, lon
   a.F = n_taps;
   a.level = level;
   a.add_constant = add_constant != 0;
-  for (int k = 0; k < kSmoothMaxTaps; ++k) {
-    a.dec_lo[k] = k < n_taps ? static_cast<float>(dec_lo[k]) : 0.f;
-    a.rec_lo[k] = k < n_taps ? static_cast<float>(rec_lo[k]) : 0.f;
-  }
+  pad_taps(dec_lo, n_taps, a.dec_lo);
+  pad_taps(rec_lo, n_taps, a.rec_lo);
+  pyramid_lengths(static_cast<int>(n), n_taps, level, a.len);
   auto r4 = [](int m) { return (m + 3) & ~3; };
   a.ext = r4(n_taps);
-  a.len[0] = static_cast<int>(n);
   a.off[0] = a.ext;
   int smax[2] = {0, 0};
   for (int j = 1; j <= kSmoothMaxLevel; ++j) {
-    a.len[j] = j <= level ? (a.len[j - 1] + n_taps - 1) / 2 : 0;
     a.off[j] = a.off[j - 1] + r4(a.len[j - 1]) + 2 * a.ext;
     if (j <= level && a.len[j] + 1 > smax[j & 1]) smax[j & 1] = a.len[j] + 1;
   }
@@ -248,13 +228,8 @@ extern "C" int wtmi_dwt_smooth(const float* x, const float* y, long long ld, lon
   const size_t lds = static_cast<size_t>(base + a.nch * per) * sizeof(float);
   if (lds > static_cast<size_t>(kSmoothLdsMax) || batch * a.groups > 0x7fffffffll) return kErrUnsupported;
   auto* kern = stats ? dwt_smooth_kernel<true> : dwt_smooth_kernel<false>;
-  if (lds > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds));
-  // about two output pairs of the finest level per thread: app-sized rows (n ~ 500 .. 1400)
-  // get 128 .. 384 threads instead of mostly idle waves
-  int threads = (static_cast<int>((n + 3) / 4) + kWave - 1) / kWave * kWave;
-  threads = threads < kWave ? kWave : threads > kSmoothMaxThreads ? kSmoothMaxThreads : threads;
+  allow_lds(kern, lds);
+  const int threads = threads_for(n, 4, kSmoothMaxThreads);  // about two output pairs of the finest level each
   hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(batch * a.groups)), dim3(threads), lds,
                      static_cast<hipStream_t>(stream), x, y, ld, a, smooth, stats);
   return launch_status();

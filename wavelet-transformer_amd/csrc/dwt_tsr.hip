@@ -24,10 +24,10 @@
 
 namespace wtmi {
 
-constexpr int kTsrMaxTaps = 40;
+constexpr int kTsrMaxTaps = kPyrMaxTaps;
 constexpr int kTsrMaxN = 8192;       // 2 n floats of LDS: two workgroups per CU
 constexpr int kTsrMaxThreads = 512;
-constexpr int kTsrMaxLevel = 60;
+constexpr int kTsrMaxLevel = kPyrMaxLevel;
 constexpr int kOlsThreads = 256;
 
 enum : int { kDecLo = 0, kDecHi = 1, kRecLo = 2, kRecHi = 3 };
@@ -80,25 +80,13 @@ dwt_tsr_kernel(const float* __restrict__ x, const float* __restrict__ y, long lo
       const float* g = s == 0 ? gx : gy;
       float* cur = R0;
       step_sync(prev_small, false);  // the other series' last step has read R0 / R1
-      if (aligned16(g)) {
-        const int n4 = n >> 2;
-        for (int i = tid; i < n4; i += T)
-          reinterpret_cast<float4*>(cur)[i] = reinterpret_cast<const float4*>(g)[i];
-        for (int i = 4 * n4 + tid; i < n; i += T) cur[i] = g[i];
-      } else {
-        for (int i = tid; i < n; i += T) cur[i] = g[i];
-      }
+      load_row(cur, g, n);
       // analysis: approximations down to level jt, where the component's own array is kept
       for (int j = 1; j <= jt; ++j) {
         const int m = a.len[j - 1], M = a.len[j];
         const bool small = M <= kWave;
         step_sync(prev_small, small);
-        const int lim = small ? kWave : T;
-        if (tid < lim)
-          for (int e = tid; e < 2 * F - 3; e += lim) {
-            const int idx = e < F - 2 ? e - (F - 2) : m + e - (F - 2);
-            cur[idx] = cur[reflect(idx, m)];
-          }
+        extend_row(cur, m, F, small ? kWave : T);
         step_sync(prev_small, small);
         float* dst = (s == 0 && jt == 1) ? R2 : (cur == R0 ? R1 : R0);
         const int bank = (j == jt && detail) ? kDecHi : kDecLo;
@@ -234,23 +222,18 @@ extern "C" int wtmi_dwt_tsr(const float* x, const float* y, long long ld, long l
   a.F = n_taps;
   a.level = level;
   a.add_constant = add_constant != 0;
-  const double* src[4] = {dec_lo, dec_hi, rec_lo, rec_hi};
-  for (int f = 0; f < 4; ++f)
-    for (int k = 0; k < kTsrMaxTaps; ++k) a.taps[f][k] = k < n_taps ? static_cast<float>(src[f][k]) : 0.f;
-  a.len[0] = static_cast<int>(n);
-  for (int j = 1; j <= kTsrMaxLevel; ++j) a.len[j] = j <= level ? (a.len[j - 1] + n_taps - 1) / 2 : 0;
+  pad_taps(dec_lo, n_taps, a.taps[kDecLo]);
+  pad_taps(dec_hi, n_taps, a.taps[kDecHi]);
+  pad_taps(rec_lo, n_taps, a.taps[kRecLo]);
+  pad_taps(rec_hi, n_taps, a.taps[kRecHi]);
+  pyramid_lengths(static_cast<int>(n), n_taps, level, a.len);
   a.out_len = level > 0 ? 2 * a.len[1] - n_taps + 2 : a.len[0];  // pywt waverec length
   const int ext = (n_taps + 3) & ~3;
   const int cap0 = ((a.len[0] + 3) & ~3) + 2 * ext;
   const int cap1 = ((a.len[1] + 1 + 3) & ~3) + 2 * ext;
   const size_t lds = level > 0 ? static_cast<size_t>(cap0 + 2 * cap1) * sizeof(float) : 0;
-  if (lds > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwt_tsr_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  // about two output pairs of the finest level per thread: app-sized rows (n ~ 500 .. 1400)
-  // get 128 .. 384 threads instead of mostly idle waves
-  int threads = (static_cast<int>((n + 3) / 4) + kWave - 1) / kWave * kWave;
-  threads = threads < kWave ? kWave : threads > kTsrMaxThreads ? kTsrMaxThreads : threads;
+  allow_lds(dwt_tsr_kernel, lds);
+  const int threads = threads_for(n, 4, kTsrMaxThreads);  // about two output pairs of the finest level each
   hipLaunchKernelGGL(dwt_tsr_kernel, dim3(static_cast<unsigned>(batch * (level + 1))), dim3(threads), lds,
                      static_cast<hipStream_t>(stream), x, y, ld, a, stats, comps, ext, cap0, cap1);
   return launch_status();

@@ -866,13 +866,6 @@ static bool make_bank(const double* dec_lo, const double* dec_hi, int L, FilterB
   return true;
 }
 
-template <typename K>
-static void allow_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-}
-
 }  // namespace wtmi
 
 using namespace wtmi;

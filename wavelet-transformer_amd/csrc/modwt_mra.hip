@@ -36,6 +36,7 @@
 // loads that one row, applies the h~ synthesis step of its level (g~ for row J) and the g~
 // steps down to level 1.  The zero rows of the masked inverse are never read.
 #include "common.hpp"
+#include "modwt_rows.hpp"
 #include "ols.hpp"
 
 // fp32 arithmetic of this file stays on the scalar VALU forms
@@ -44,9 +45,9 @@
 namespace wtmi {
 
 constexpr int kMraMaxN = 16384;
-constexpr int kMraMaxTaps = 40;
+constexpr int kMraMaxTaps = kModwtRowsMaxTaps;
 constexpr int kMraMaxThreads = 1024;
-constexpr int kMraMaxLevel = 62;  // 2^(j-1) as a long long, as wtmi_modwt
+constexpr int kMraMaxLevel = kModwtRowsMaxLevel;
 
 struct MraArgs {
   int n, level, add_constant;
@@ -63,14 +64,6 @@ struct MraRowArgs {
   float h[kMraMaxTaps];  // dec_hi / sqrt2
   float g[kMraMaxTaps];  // dec_lo / sqrt2
 };
-
-// Series b of g (and of y in pair mode) into LDS, shifted by its first sample.
-__device__ __forceinline__ float load_shifted(const float* __restrict__ g, float* __restrict__ V, int n) {
-  const float k = g[0];
-#pragma unroll 4
-  for (int i = threadIdx.x; i < n; i += blockDim.x) V[i] = g[i] - k;
-  return k;
-}
 
 // Thread 0: offsets (d m) mod n of the kept lags, by repeated addition over the lags (d < n).
 __device__ __forceinline__ void lag_offsets(const MraArgs& a, int d, int* __restrict__ soff) {
@@ -196,15 +189,8 @@ template <int DM>
 __device__ __forceinline__ void window_lags(const float4* __restrict__ V4, int q, int ng, const MraArgs& a,
                                             float4& dv, float4& uv) {
   constexpr int HB = (7 * DM + 3) / 4;  // groups either side that the lags +-7 DM reach
-  constexpr int NB = 2 * HB + 1;
-  float f[4 * NB];
-#pragma unroll
-  for (int w = 0; w < NB; ++w) {
-    int qs = q - HB + w;
-    qs = qs < 0 ? qs + ng : (qs >= ng ? qs - ng : qs);  // ng >= 16 > HB
-    const float4 v = V4[qs];
-    f[4 * w] = v.x; f[4 * w + 1] = v.y; f[4 * w + 2] = v.z; f[4 * w + 3] = v.w;
-  }
+  float f[4 * (2 * HB + 1)];
+  load_window<HB, HB>(V4, q, ng, f);
   float rd[4], ru[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -220,17 +206,6 @@ __device__ __forceinline__ void window_lags(const float4* __restrict__ V4, int q
   }
   dv = make_float4(rd[0], rd[1], rd[2], rd[3]);
   uv = make_float4(ru[0], ru[1], ru[2], ru[3]);
-}
-
-__device__ __forceinline__ float4 add4(const float4& p, const float4& q) {
-  return make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w);
-}
-
-__device__ __forceinline__ void fma4s(float4& acc, float c, const float4& v) {
-  acc.x = fmaf(c, v.x, acc.x);
-  acc.y = fmaf(c, v.y, acc.y);
-  acc.z = fmaf(c, v.z, acc.z);
-  acc.w = fmaf(c, v.w, acc.w);
 }
 
 template <int GROUPS, bool PAIR>
@@ -289,8 +264,8 @@ modwt_mra_vec_kernel(const float* __restrict__ x, const float* __restrict__ y, l
             const int qp = q + off[t] >= ng ? q + off[t] - ng : q + off[t];
             const int qm = q - off[t] < 0 ? q - off[t] + ng : q - off[t];
             const float4 v = add4(V4[qp], V4[qm]);
-            fma4s(ad, a.h[t], v);
-            fma4s(au, a.g[t], v);
+            fma4(ad, a.h[t], v);
+            fma4(au, a.g[t], v);
           }
           dv[s] = ad;
           u[s][kk] = au;
@@ -347,15 +322,7 @@ modwt_mra_rows_kernel(const float* __restrict__ w, MraRowArgs a, float* __restri
   for (int i = tid; i < n; i += T) V[i] = src[i];
   for (int j = jr; j >= 1; --j) {
     const float* f = (j == jr && r < J) ? a.h : a.g;
-    if (tid == 0) {  // offsets (2^(j-1) l) mod n by repeated addition
-      const int d = static_cast<int>((1ll << (j - 1)) % n);
-      int o = 0;
-      for (int l = 0; l < a.L; ++l) {
-        soff[l] = o;
-        o += d;
-        if (o >= n) o -= n;
-      }
-    }
+    if (tid == 0) tap_offsets(static_cast<int>((1ll << (j - 1)) % n), n, a.L, soff);
     __syncthreads();
     float v[PER];
 #pragma unroll
@@ -380,21 +347,6 @@ modwt_mra_rows_kernel(const float* __restrict__ w, MraRowArgs a, float* __restri
   __syncthreads();
   for (int i = tid; i < n; i += T) dst[i] = V[i];
 }
-
-template <typename K>
-static void allow_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(bytes));
-}
-
-// PER samples per thread in whole waves: app-sized rows get a few waves instead of idle ones
-static int mra_threads(int n, int per) {
-  const int t = ((n + per - 1) / per + kWave - 1) / kWave * kWave;
-  return t < kWave ? kWave : (t > kMraMaxThreads ? kMraMaxThreads : t);
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace wtmi
 
@@ -448,19 +400,19 @@ extern "C" int wtmi_modwt_mra(const float* x, const float* y, long long ld, long
     const size_t lds = static_cast<size_t>(pair ? 2 : 1) * ni * sizeof(float);
     const int ng = ni / 4;
     if (ng <= kMraMaxThreads) {
-      const int t = mra_threads(ng, 1);
+      const int t = threads_for(ng, 1, kMraMaxThreads);
       if (pair) launch(modwt_mra_vec_kernel<1, true>, t, lds); else launch(modwt_mra_vec_kernel<1, false>, t, lds);
     } else {
-      const int t = mra_threads(ng, 4);
+      const int t = threads_for(ng, 4, kMraMaxThreads);
       if (pair) launch(modwt_mra_vec_kernel<4, true>, t, lds); else launch(modwt_mra_vec_kernel<4, false>, t, lds);
     }
   } else {
     const size_t lds = static_cast<size_t>(pair ? 2 : 1) * ((ni + 3) & ~3) * sizeof(float);
     if (ni <= 4 * kMraMaxThreads) {
-      const int t = mra_threads(ni, 4);
+      const int t = threads_for(ni, 4, kMraMaxThreads);
       if (pair) launch(modwt_mra_kernel<4, true>, t, lds); else launch(modwt_mra_kernel<4, false>, t, lds);
     } else {
-      const int t = mra_threads(ni, 16);
+      const int t = threads_for(ni, 16, kMraMaxThreads);
       if (pair) launch(modwt_mra_kernel<16, true>, t, lds); else launch(modwt_mra_kernel<16, false>, t, lds);
     }
   }
@@ -478,19 +430,17 @@ extern "C" int wtmi_modwt_mra_rows(const float* w, long long batch, long long n,
   a.n = static_cast<int>(n);
   a.level = level;
   a.L = n_taps;
-  const double r = 1.0 / sqrt(2.0);
-  for (int l = 0; l < n_taps; ++l) {
-    a.h[l] = static_cast<float>(dec_hi[l] * r);
-    a.g[l] = static_cast<float>(dec_lo[l] * r);
-  }
+  scaled_bank(dec_lo, dec_hi, n_taps, a.h, a.g);
   const size_t lds = static_cast<size_t>((a.n + 3) & ~3) * sizeof(float);
   const unsigned grid = static_cast<unsigned>(batch * (level + 1));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.n <= 4 * kMraMaxThreads) {
-    hipLaunchKernelGGL(modwt_mra_rows_kernel<4>, dim3(grid), dim3(mra_threads(a.n, 4)), lds, st, w, a, mra);
+    hipLaunchKernelGGL(modwt_mra_rows_kernel<4>, dim3(grid), dim3(threads_for(a.n, 4, kMraMaxThreads)), lds, st, w,
+                       a, mra);
   } else {
     allow_lds(modwt_mra_rows_kernel<16>, lds);
-    hipLaunchKernelGGL(modwt_mra_rows_kernel<16>, dim3(grid), dim3(mra_threads(a.n, 16)), lds, st, w, a, mra);
+    hipLaunchKernelGGL(modwt_mra_rows_kernel<16>, dim3(grid), dim3(threads_for(a.n, 16, kMraMaxThreads)), lds, st, w,
+                       a, mra);
   }
   return launch_status();
 }

@@ -26,6 +26,7 @@
 // The passes run on x - x[0] and y - y[0]: the fp32-rounded h~ does not sum to exactly 0, so a
 // large mean would leak into the detail rows; a constant series gives W = 0 exactly.
 #include "common.hpp"
+#include "modwt_rows.hpp"
 #include "ols.hpp"
 
 // fp32 arithmetic of this file stays on the scalar VALU forms
@@ -35,10 +36,10 @@ namespace wtmi {
 
 constexpr int kWcMaxN = 16384;     // two smooth rows: 128 KiB of LDS
 constexpr int kWcMaxLagN = 8192;   // with the two coefficient rows beside them
-constexpr int kWcMaxTaps = 40;
+constexpr int kWcMaxTaps = kModwtRowsMaxTaps;
 constexpr int kWcMaxLag = 64;
 constexpr int kWcMaxThreads = 1024;
-constexpr int kWcMaxLevel = 62;
+constexpr int kWcMaxLevel = kModwtRowsMaxLevel;
 constexpr int kWcLagsPerPass = 8;  // fp64 accumulators a lane carries through one walk over t
 
 struct WcArgs {
@@ -47,40 +48,6 @@ struct WcArgs {
   float h[kWcMaxTaps];  // dec_hi / sqrt2
   float g[kWcMaxTaps];  // dec_lo / sqrt2
 };
-
-struct Mom3 {
-  double sxx, sxy, syy;
-};
-
-// Sum over the workgroup, valid (and bitwise the same) in every thread; red: 3 doubles per wave.
-// Its barrier ends the caller's LDS reads and publishes its LDS writes.
-__device__ __forceinline__ Mom3 block_sum3(Mom3 m, double* red) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  m.sxx = wave_sum(m.sxx);
-  m.sxy = wave_sum(m.sxy);
-  m.syy = wave_sum(m.syy);
-  if (lane == 0) {
-    red[3 * wave + 0] = m.sxx;
-    red[3 * wave + 1] = m.sxy;
-    red[3 * wave + 2] = m.syy;
-  }
-  __syncthreads();
-  Mom3 r{0.0, 0.0, 0.0};
-  const int nw = blockDim.x / kWave;
-  for (int w = 0; w < nw; ++w) {
-    r.sxx += red[3 * w + 0];
-    r.sxy += red[3 * w + 1];
-    r.syy += red[3 * w + 2];
-  }
-  return r;
-}
-
-__device__ __forceinline__ float wc_load_shifted(const float* __restrict__ g, float* __restrict__ V, int n) {
-  const float k = g[0];
-#pragma unroll 4
-  for (int i = threadIdx.x; i < n; i += blockDim.x) V[i] = g[i] - k;
-  return k;
-}
 
 // What a level's epilogue and its lag pass share (the same values in every thread).
 struct WcLevel {
@@ -201,17 +168,10 @@ modwt_wcorr_kernel(const float* __restrict__ x, const float* __restrict__ y, lon
   float* V[2] = {sm, sm + np};
   float* W[2] = {sm + 2 * np, sm + 3 * np};  // LAGS only
 #pragma unroll
-  for (int s = 0; s < P; ++s) wc_load_shifted((s == 0 ? x : y) + b * ld, V[s], n);
+  for (int s = 0; s < P; ++s) load_shifted((s == 0 ? x : y) + b * ld, V[s], n);
   int d = 1 % n, t0 = 0, dsat = 1;
   for (int j = 1; j <= J; ++j) {
-    if (tid == 0) {  // offsets (d l) mod n by repeated addition (d < n)
-      int o = 0;
-      for (int l = 0; l < L; ++l) {
-        soff[l] = o;
-        o += d;
-        if (o >= n) o -= n;
-      }
-    }
+    if (tid == 0) tap_offsets(d, n, L, soff);
     __syncthreads();  // V_{j-1} and the offsets are in place; the last level's lag pass is over
     next_t0(a, t0, dsat);
     float u[P][PER];
@@ -275,15 +235,8 @@ template <int DM>
 __device__ __forceinline__ void window_taps(const float4* __restrict__ V4, int q, int ng, const WcArgs& a,
                                             float4& wv, float4& uv) {
   constexpr int HB = (7 * DM + 3) / 4;  // groups behind q that the taps t - 7 DM reach
-  constexpr int NB = HB + 1;
-  float f[4 * NB];
-#pragma unroll
-  for (int w = 0; w < NB; ++w) {
-    int qs = q - HB + w;
-    qs = qs < 0 ? qs + ng : qs;  // ng >= 16 > HB
-    const float4 v = V4[qs];
-    f[4 * w] = v.x; f[4 * w + 1] = v.y; f[4 * w + 2] = v.z; f[4 * w + 3] = v.w;
-  }
+  float f[4 * (HB + 1)];
+  load_window<HB, 0>(V4, q, ng, f);
   float rw[4], ru[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -299,26 +252,6 @@ __device__ __forceinline__ void window_taps(const float4* __restrict__ V4, int q
   uv = make_float4(ru[0], ru[1], ru[2], ru[3]);
 }
 
-__device__ __forceinline__ void wc_fma4(float4& acc, float c, const float4& v) {
-  acc.x = fmaf(c, v.x, acc.x);
-  acc.y = fmaf(c, v.y, acc.y);
-  acc.z = fmaf(c, v.z, acc.z);
-  acc.w = fmaf(c, v.w, acc.w);
-}
-
-template <bool PAIR>
-__device__ __forceinline__ void mom_add(Mom3& m, float wx, float wy, bool in) {
-  if (in) {
-    const double dx = static_cast<double>(wx);
-    m.sxx = fma(dx, dx, m.sxx);
-    if (PAIR) {
-      const double dy = static_cast<double>(wy);
-      m.sxy = fma(dx, dy, m.sxy);
-      m.syy = fma(dy, dy, m.syy);
-    }
-  }
-}
-
 template <int GROUPS, bool PAIR, bool LAGS>
 __global__ void __launch_bounds__(kWcMaxThreads, PAIR ? 4 : 8)
 modwt_wcorr_vec_kernel(const float* __restrict__ x, const float* __restrict__ y, long long ld, WcArgs a,
@@ -331,7 +264,7 @@ modwt_wcorr_vec_kernel(const float* __restrict__ x, const float* __restrict__ y,
   float* V[2] = {sm, sm + n};
   float* W[2] = {sm + 2 * n, sm + 3 * n};  // LAGS only
 #pragma unroll
-  for (int s = 0; s < P; ++s) wc_load_shifted((s == 0 ? x : y) + b * ld, V[s], n);
+  for (int s = 0; s < P; ++s) load_shifted((s == 0 ? x : y) + b * ld, V[s], n);
   int d = 1, t0 = 0, dsat = 1;  // n >= 64
   for (int j = 1; j <= J; ++j) {
     __syncthreads();  // V_{j-1} is in place; the last level's lag pass is over
@@ -362,8 +295,8 @@ modwt_wcorr_vec_kernel(const float* __restrict__ x, const float* __restrict__ y,
           for (int l = 0; l < 8; ++l) {
             const int qs = q - off[l] < 0 ? q - off[l] + ng : q - off[l];
             const float4 v = V4[qs];
-            wc_fma4(aw, a.h[l], v);
-            wc_fma4(au, a.g[l], v);
+            fma4(aw, a.h[l], v);
+            fma4(au, a.g[l], v);
           }
           wv[s] = aw;
           u[s][kk] = au;
@@ -392,19 +325,6 @@ modwt_wcorr_vec_kernel(const float* __restrict__ x, const float* __restrict__ y,
   if (PAIR) wc_intervals(stats + b * J * 8, J, a.z);
 }
 
-template <typename K>
-static void wc_allow_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(bytes));
-}
-
-// `per` items per thread in whole waves: app-sized rows get a few waves instead of idle ones
-static int wc_threads(int items, int per) {
-  const int t = ((items + per - 1) / per + kWave - 1) / kWave * kWave;
-  return t < kWave ? kWave : (t > kWcMaxThreads ? kWcMaxThreads : t);
-}
-
 }  // namespace wtmi
 
 #pragma clang attribute pop
@@ -430,16 +350,12 @@ extern "C" int wtmi_modwt_wcorr(const float* x, const float* y, long long ld, lo
   a.periodic = boundary == 0;
   a.max_lag = max_lag;
   a.z = z;
-  const double r = 1.0 / sqrt(2.0);
-  for (int l = 0; l < n_taps; ++l) {
-    a.h[l] = static_cast<float>(dec_hi[l] * r);
-    a.g[l] = static_cast<float>(dec_lo[l] * r);
-  }
+  scaled_bank(dec_lo, dec_hi, n_taps, a.h, a.g);
   const bool pair = y != nullptr, lags = max_lag > 0;
   const int ni = a.n, rows = lags ? 4 : (pair ? 2 : 1);
   hipStream_t st = static_cast<hipStream_t>(stream);
   auto launch = [&](auto kernel, int threads, size_t lds) {
-    wc_allow_lds(kernel, lds);
+    allow_lds(kernel, lds);
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(batch)), dim3(threads), lds, st, x, y, ld, a, stats,
                        xcorr);
   };
@@ -452,24 +368,24 @@ extern "C" int wtmi_modwt_wcorr(const float* x, const float* y, long long ld, lo
     const int ng = ni / 4;
     if (ng <= kWcMaxThreads)
       pick(modwt_wcorr_vec_kernel<1, false, false>, modwt_wcorr_vec_kernel<1, true, false>,
-           modwt_wcorr_vec_kernel<1, true, true>, wc_threads(ng, 1), lds);
+           modwt_wcorr_vec_kernel<1, true, true>, threads_for(ng, 1, kWcMaxThreads), lds);
     else if (ng <= 2 * kWcMaxThreads)
       pick(modwt_wcorr_vec_kernel<2, false, false>, modwt_wcorr_vec_kernel<2, true, false>,
-           modwt_wcorr_vec_kernel<2, true, true>, wc_threads(ng, 2), lds);
+           modwt_wcorr_vec_kernel<2, true, true>, threads_for(ng, 2, kWcMaxThreads), lds);
     else  // n > 8192: no lag rows
       pick(modwt_wcorr_vec_kernel<4, false, false>, modwt_wcorr_vec_kernel<4, true, false>,
-           modwt_wcorr_vec_kernel<4, true, false>, wc_threads(ng, 4), lds);
+           modwt_wcorr_vec_kernel<4, true, false>, threads_for(ng, 4, kWcMaxThreads), lds);
   } else {
     const size_t lds = static_cast<size_t>(rows) * ((ni + 3) & ~3) * sizeof(float);
     if (ni <= 4 * kWcMaxThreads)
       pick(modwt_wcorr_kernel<4, false, false>, modwt_wcorr_kernel<4, true, false>,
-           modwt_wcorr_kernel<4, true, true>, wc_threads(ni, 4), lds);
+           modwt_wcorr_kernel<4, true, true>, threads_for(ni, 4, kWcMaxThreads), lds);
     else if (ni <= 8 * kWcMaxThreads)
       pick(modwt_wcorr_kernel<8, false, false>, modwt_wcorr_kernel<8, true, false>,
-           modwt_wcorr_kernel<8, true, true>, wc_threads(ni, 8), lds);
+           modwt_wcorr_kernel<8, true, true>, threads_for(ni, 8, kWcMaxThreads), lds);
     else  // n > 8192: no lag rows
       pick(modwt_wcorr_kernel<16, false, false>, modwt_wcorr_kernel<16, true, false>,
-           modwt_wcorr_kernel<16, true, false>, wc_threads(ni, 16), lds);
+           modwt_wcorr_kernel<16, true, false>, threads_for(ni, 16, kWcMaxThreads), lds);
   }
   return launch_status();
 }

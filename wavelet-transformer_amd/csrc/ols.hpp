@@ -1,5 +1,6 @@
-// fp64 moments of a float32 row pair and the OLS epilogue on them, shared by the time-scale
-// regression kernels (dwt_tsr.hip: K17 / K18; modwt_mra.hip: K19).
+// fp64 moments of a float32 row pair, their workgroup reductions and the OLS epilogue on the
+// five-sum form, shared by the fused kernels: Mom / block_sum / ols_store by dwt_tsr.hip (K17 /
+// K18), modwt_mra.hip (K19) and dwt_smooth.hip (K21); Mom3 / block_sum3 by modwt_wcorr.hip (K22).
 #pragma once
 
 #include "common.hpp"
@@ -34,6 +35,8 @@ __device__ __forceinline__ Mom wave_sum(Mom m) {
   return Mom{wave_sum(m.sx), wave_sum(m.sy), wave_sum(m.sxx), wave_sum(m.sxy), wave_sum(m.syy)};
 }
 
+// The two block sums below keep their own wave-to-LDS halves: written once over a parameter
+// pack, the register moves around the shuffle calls changed in every kernel that reduces.
 // sum over the workgroup, valid in thread 0; red: 5 doubles per wave
 __device__ __forceinline__ Mom block_sum(Mom m, double* red) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -57,6 +60,47 @@ __device__ __forceinline__ Mom block_sum(Mom m, double* red) {
     }
   }
   return m;
+}
+
+// ---- the three lag-0 sums of a coefficient row pair (no shift: the rows are details) ------
+struct Mom3 {
+  double sxx, sxy, syy;
+};
+
+template <bool PAIR>
+__device__ __forceinline__ void mom_add(Mom3& m, float wx, float wy, bool in) {
+  if (in) {
+    const double dx = static_cast<double>(wx);
+    m.sxx = fma(dx, dx, m.sxx);
+    if (PAIR) {
+      const double dy = static_cast<double>(wy);
+      m.sxy = fma(dx, dy, m.sxy);
+      m.syy = fma(dy, dy, m.syy);
+    }
+  }
+}
+
+// Sum over the workgroup, valid (and bitwise the same) in every thread; red: 3 doubles per wave.
+// Its barrier ends the caller's LDS reads and publishes its LDS writes.
+__device__ __forceinline__ Mom3 block_sum3(Mom3 m, double* red) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  m.sxx = wave_sum(m.sxx);
+  m.sxy = wave_sum(m.sxy);
+  m.syy = wave_sum(m.syy);
+  if (lane == 0) {
+    red[3 * wave + 0] = m.sxx;
+    red[3 * wave + 1] = m.sxy;
+    red[3 * wave + 2] = m.syy;
+  }
+  __syncthreads();
+  Mom3 r{0.0, 0.0, 0.0};
+  const int nw = blockDim.x / kWave;
+  for (int w = 0; w < nw; ++w) {
+    r.sxx += red[3 * w + 0];
+    r.sxy += red[3 * w + 1];
+    r.syy += red[3 * w + 2];
+  }
+  return r;
 }
 
 // The regression of y on [1, x] (add_constant) or on x alone, from the shifted moments of nobs

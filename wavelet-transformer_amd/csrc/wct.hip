@@ -2046,9 +2046,7 @@ static int wct_morlet_impl(const float* x1, const float* x2, long long ld, long 
   if (logn < 4) {  // n0 <= 8: below the FFT engine's minimum row
     const size_t lds = static_cast<size_t>(n_scales) * n0 * sizeof(float4);
     if (lds > kWctDirectMaxLds || batch > 0x7fffffffll) return kErrUnsupported;
-    if (lds > 65536)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wct_direct_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    allow_lds(wct_direct_kernel, lds);
     hipLaunchKernelGGL(wct_direct_kernel, dim3(static_cast<unsigned>(batch)), dim3(256), lds, st, a,
                        1 << logn, boxcar, out_coh);
     return launch_status();

@@ -434,6 +434,10 @@ def _taps(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _tp(arr: np.ndarray):
+    return arr.ctypes.data_as(VP)
+
+
 def _out(out, shape, dev):
     if out is None:
         return torch.empty(shape, dtype=torch.float32, device=dev)
@@ -452,8 +456,8 @@ def modwt(x: torch.Tensor, dec_lo, dec_hi, level: int, out: Optional[torch.Tenso
     w = _out(out, (B, level + 1, n), dev)
     ws = _scratch(_lib.call("wtmi_modwt_workspace_bytes", B, n, int(level)), dev)
     with torch.cuda.device(dev):
-        _lib.call("wtmi_modwt", _ptr(x), x.stride(0), B, n, lo.ctypes.data_as(VP),
-                  hi.ctypes.data_as(VP), lo.size, int(level), _ptr(w), _ptr(ws), _stream(dev))
+        _lib.call("wtmi_modwt", _ptr(x), x.stride(0), B, n, _tp(lo), _tp(hi), lo.size, int(level),
+                  _ptr(w), _ptr(ws), _stream(dev))
     return w
 
 
@@ -477,7 +481,7 @@ def imodwt(w: torch.Tensor, dec_lo, dec_hi, keep_mask: Optional[int] = None,
     x = _out(out, (B, n), dev)
     ws = _scratch(_lib.call("wtmi_modwt_workspace_bytes", B, n, R - 1), dev)
     with torch.cuda.device(dev):
-        _lib.call("wtmi_imodwt", _ptr(w), B, n, lo.ctypes.data_as(VP), hi.ctypes.data_as(VP),
+        _lib.call("wtmi_imodwt", _ptr(w), B, n, _tp(lo), _tp(hi),
                   lo.size, R - 1, C.c_ulonglong(keep), _ptr(x), x.stride(0), _ptr(ws), _stream(dev))
     return x
 
@@ -501,8 +505,8 @@ def wavedec(x: torch.Tensor, dec_lo, dec_hi, level: int):
     coeffs = torch.empty((B, sum(lens)), dtype=torch.float32, device=dev)
     ws = _scratch(_lib.call("wtmi_dwt_workspace_bytes", B, n, lo.size, 1), dev)
     with torch.cuda.device(dev):
-        _lib.call("wtmi_wavedec", _ptr(x), x.stride(0), B, n, lo.ctypes.data_as(VP),
-                  hi.ctypes.data_as(VP), lo.size, int(level), _ptr(coeffs), _ptr(ws), _stream(dev))
+        _lib.call("wtmi_wavedec", _ptr(x), x.stride(0), B, n, _tp(lo), _tp(hi), lo.size, int(level),
+                  _ptr(coeffs), _ptr(ws), _stream(dev))
     return coeffs, lens
 
 
@@ -526,8 +530,8 @@ def waverec(coeffs: torch.Tensor, n: int, rec_lo, rec_hi, level: int,
         return coeffs[:, None, :n] * keep[None, :, None]
     ws = _scratch(_lib.call("wtmi_dwt_workspace_bytes", B, n, lo.size, len(keep_masks)), dev)
     with torch.cuda.device(dev):
-        _lib.call("wtmi_waverec", _ptr(coeffs), B, n, lo.ctypes.data_as(VP),
-                  hi.ctypes.data_as(VP), lo.size, int(level), _ptr(masks), len(keep_masks),
+        _lib.call("wtmi_waverec", _ptr(coeffs), B, n, _tp(lo), _tp(hi), lo.size, int(level),
+                  _ptr(masks), len(keep_masks),
                   _ptr(out), out_len, _ptr(ws), _stream(dev))
     return out
 
@@ -553,6 +557,40 @@ def _ols_rows(x, y, what):
         raise ValueError(f"{what}: expected [n] or [batch, n] rows, got shape {tuple(x.shape)}")
 
 
+def _series_or_pair(x, y, what, has_output):
+    """Operand checks and placement of "x alone or an (x, y) pair": (device, x rows, y rows or
+    None).  has_output: whether anything is requested that a single series can deliver."""
+    if y is None:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
+                or x.shape[-1] < 1:
+            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
+        if not has_output:
+            raise ValueError(f"{what}: no output requested")
+        return _check_dev(x), _rows(x), None
+    _ols_rows(x, y, what)
+    return (_check_dev(x, y), *_pair_rows(x, y))
+
+
+def _int_level(level, lo, hi, what):
+    """level as an int in lo..hi (hi None: unbounded); what: the message's prefix, or None."""
+    if int(level) != level or level < lo or (hi is not None and level > hi):
+        rng = f">= {lo}" if hi is None else f"in {lo}..{hi}"
+        raise ValueError(f"{what + ': ' if what else ''}level must be an integer {rng}, got {level!r}")
+    return int(level)
+
+
+def _bank(what, **taps):
+    """Two or four named tap arrays as contiguous float64: 1-D, the same number (>= 2) of taps."""
+    arrs = [_taps(a) for a in taps.values()]
+    F = arrs[0].size
+    if any(t.ndim != 1 or t.size != F for t in arrs) or F < 2:
+        names = list(taps)
+        got = f"{arrs[0].shape} and {arrs[1].shape}" if len(arrs) == 2 else f"{[t.shape for t in arrs]}"
+        raise ValueError(f"{what + ': ' if what else ''}{', '.join(names[:-1])} and {names[-1]} must hold the "
+                         f"same number of taps (>= 2), got {got}")
+    return arrs
+
+
 def rows_ols(x_rows: torch.Tensor, y_rows: torch.Tensor, add_constant: bool = True) -> torch.Tensor:
     """OLS of y row r on [1, x row r] (or on the x row alone) for float32 [R, n] row pairs:
     [R, 8] float64 = ``STATS`` (wtmi_rows_ols; nobs = n)."""
@@ -576,14 +614,9 @@ def dwt_time_scale_regression(x: torch.Tensor, y: torch.Tensor, dec_lo, dec_hi, 
     ``TSR_MAX_TAPS`` taps) take ONE fused launch; longer ones compose wavedec, waverec with the
     level + 1 one-bit masks and rows_ols."""
     _ols_rows(x, y, "dwt_time_scale_regression")
-    if int(level) != level or level < 0:
-        raise ValueError(f"level must be an integer >= 0, got {level!r}")
-    level = int(level)
-    taps = [_taps(a) for a in (dec_lo, dec_hi, rec_lo, rec_hi)]
+    level = _int_level(level, 0, None, None)
+    taps = _bank(None, dec_lo=dec_lo, dec_hi=dec_hi, rec_lo=rec_lo, rec_hi=rec_hi)
     F = taps[0].size
-    if any(t.ndim != 1 or t.size != F for t in taps) or F < 2:
-        raise ValueError("dec_lo, dec_hi, rec_lo and rec_hi must hold the same number of taps "
-                         f"(>= 2), got {[t.shape for t in taps]}")
     dev = _check_dev(x, y)
     x, y = _pair_rows(x, y)
     B, n = x.shape
@@ -600,7 +633,7 @@ def dwt_time_scale_regression(x: torch.Tensor, y: torch.Tensor, dec_lo, dec_hi, 
     comps = torch.empty((B, 2, level + 1, out_len), dtype=torch.float32, device=dev) \
         if want_components else None
     with torch.cuda.device(dev):
-        _lib.call("wtmi_dwt_tsr", _ptr(x), _ptr(y), x.stride(0), B, n, *(t.ctypes.data_as(VP) for t in taps),
+        _lib.call("wtmi_dwt_tsr", _ptr(x), _ptr(y), x.stride(0), B, n, *map(_tp, taps),
                   F, level, int(bool(add_constant)), _ptr(stats), _ptr(comps), _stream(dev))
     return {"stats": stats, "components": comps}
 
@@ -619,25 +652,9 @@ def dwt_smooth(x: torch.Tensor, dec_lo, rec_lo, level: int, *, y: Optional[torch
     trim and rows_ols compose, with the high-pass pair taken as the quadrature mirror of the
     low-pass one (dec_hi[k] = (-1)^(k+1) rec_lo[k], rec_hi[k] = (-1)^k dec_lo[k]: every pywt bank)."""
     what = "dwt_smooth"
-    if int(level) != level or not 1 <= level <= SMOOTH_MAX_LEVEL:
-        raise ValueError(f"{what}: level must be an integer in 1..{SMOOTH_MAX_LEVEL}, got {level!r}")
-    level = int(level)
-    lo_d, lo_r = _taps(dec_lo), _taps(rec_lo)
-    if lo_d.ndim != 1 or lo_d.shape != lo_r.shape or lo_d.size < 2:
-        raise ValueError(f"{what}: dec_lo and rec_lo must hold the same number of taps (>= 2), got "
-                         f"{lo_d.shape} and {lo_r.shape}")
-    if y is None:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
-                or x.shape[-1] < 1:
-            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
-        if not want_smooth:
-            raise ValueError(f"{what}: no output requested")
-        dev = _check_dev(x)
-        x = _rows(x)
-    else:
-        _ols_rows(x, y, what)
-        dev = _check_dev(x, y)
-        x, y = _pair_rows(x, y)
+    level = _int_level(level, 1, SMOOTH_MAX_LEVEL, what)
+    lo_d, lo_r = _bank(what, dec_lo=dec_lo, rec_lo=rec_lo)
+    dev, x, y = _series_or_pair(x, y, what, want_smooth)
     B, n = x.shape
     F = lo_d.size
     if n > TSR_MAX_N or F % 2 or F > TSR_MAX_TAPS:
@@ -652,8 +669,8 @@ def dwt_smooth(x: torch.Tensor, dec_lo, rec_lo, level: int, *, y: Optional[torch
     smooth = torch.empty((B, level, n), dtype=torch.float32, device=dev) if want_smooth else None
     stats = torch.empty((B, level, 8), dtype=torch.float64, device=dev) if y is not None else None
     with torch.cuda.device(dev):
-        _lib.call("wtmi_dwt_smooth", _ptr(x), _ptr(y), x.stride(0), B, n, lo_d.ctypes.data_as(VP),
-                  lo_r.ctypes.data_as(VP), F, level, int(bool(add_constant)), _ptr(smooth), _ptr(stats),
+        _lib.call("wtmi_dwt_smooth", _ptr(x), _ptr(y), x.stride(0), B, n, _tp(lo_d), _tp(lo_r), F,
+                  level, int(bool(add_constant)), _ptr(smooth), _ptr(stats),
                   _stream(dev))
     return {"smooth": smooth, "stats": stats}
 
@@ -661,20 +678,7 @@ def dwt_smooth(x: torch.Tensor, dec_lo, rec_lo, level: int, *, y: Optional[torch
 # ------------------------------------------------------------------- MODWT MRA
 MRA_MAX_N = 16384   # longest row of the fused kernels (include/wtmi.h: wtmi_modwt_mra)
 MRA_MAX_TAPS = 40
-
-
-def _mra_level(level, what):
-    if int(level) != level or not 1 <= level <= 62:
-        raise ValueError(f"{what}: level must be an integer in 1..62, got {level!r}")
-    return int(level)
-
-
-def _mra_taps(dec_lo, dec_hi, what):
-    lo, hi = _taps(dec_lo), _taps(dec_hi)
-    if lo.ndim != 1 or lo.shape != hi.shape or lo.size < 2:
-        raise ValueError(f"{what}: dec_lo and dec_hi must hold the same number of taps (>= 2), got "
-                         f"{lo.shape} and {hi.shape}")
-    return lo, hi
+MRA_MAX_LEVEL = 62  # the a-trous dilation 2^(level - 1) as a long long (wtmi_modwt_mra, _rows, wtmi_modwt_wcorr)
 
 
 def _masked_rows(w, lo, hi):
@@ -692,20 +696,9 @@ def modwt_mra(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torch.
     samples and filters of at most ``MRA_MAX_TAPS`` taps take ONE fused launch
     (wtmi_modwt_mra); beyond, modwt, one-bit-mask imodwt, suffix sums and rows_ols compose."""
     what = "modwt_mra"
-    level = _mra_level(level, what)
-    lo, hi = _mra_taps(dec_lo, dec_hi, what)
-    if y is None:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
-                or x.shape[-1] < 1:
-            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
-        if not (want_components or want_smooths):
-            raise ValueError(f"{what}: no output requested")
-        dev = _check_dev(x)
-        x = _rows(x)
-    else:
-        _ols_rows(x, y, what)
-        dev = _check_dev(x, y)
-        x, y = _pair_rows(x, y)
+    level = _int_level(level, 1, MRA_MAX_LEVEL, what)
+    lo, hi = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi)
+    dev, x, y = _series_or_pair(x, y, what, want_components or want_smooths)
     B, n = x.shape
     P = 1 if y is None else 2
     if n > MRA_MAX_N or lo.size > MRA_MAX_TAPS:
@@ -719,8 +712,8 @@ def modwt_mra(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torch.
     smooths = torch.empty((B, P, level, n), dtype=torch.float32, device=dev) if want_smooths else None
     stats = torch.empty((B, level + 1, 8), dtype=torch.float64, device=dev) if y is not None else None
     with torch.cuda.device(dev):
-        _lib.call("wtmi_modwt_mra", _ptr(x), _ptr(y), x.stride(0), B, n, lo.ctypes.data_as(VP),
-                  hi.ctypes.data_as(VP), lo.size, level, int(bool(add_constant)), _ptr(comps),
+        _lib.call("wtmi_modwt_mra", _ptr(x), _ptr(y), x.stride(0), B, n, _tp(lo), _tp(hi), lo.size,
+                  level, int(bool(add_constant)), _ptr(comps),
                   _ptr(smooths), _ptr(stats), _stream(dev))
     return {"components": comps, "smooths": smooths, "stats": stats}
 
@@ -730,19 +723,19 @@ def modwt_mra_rows(w: torch.Tensor, dec_lo, dec_hi) -> torch.Tensor:
     modwtmra(w, filters)): float32 [J + 1, n] or [B, J + 1, n] -> [B, J + 1, n].  One launch
     (wtmi_modwt_mra_rows) within ``MRA_MAX_N`` / ``MRA_MAX_TAPS``; one-bit-mask imodwt beyond."""
     what = "modwt_mra_rows"
-    lo, hi = _mra_taps(dec_lo, dec_hi, what)
+    lo, hi = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi)
     if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() not in (2, 3) \
             or w.shape[-2] < 2 or w.shape[-1] < 1:
         raise ValueError(f"{what}: w must be float32 [levels + 1, n] or [batch, levels + 1, n] rows")
     dev = _check_dev(w)
     w = (w.unsqueeze(0) if w.dim() == 2 else w).contiguous()
     B, R, n = w.shape
-    _mra_level(R - 1, what)
+    _int_level(R - 1, 1, MRA_MAX_LEVEL, what)
     if n > MRA_MAX_N or lo.size > MRA_MAX_TAPS:
         return _masked_rows(w, lo, hi)
     out = torch.empty_like(w)
     with torch.cuda.device(dev):
-        _lib.call("wtmi_modwt_mra_rows", _ptr(w), B, n, lo.ctypes.data_as(VP), hi.ctypes.data_as(VP),
+        _lib.call("wtmi_modwt_mra_rows", _ptr(w), B, n, _tp(lo), _tp(hi),
                   lo.size, R - 1, _ptr(out), _stream(dev))
     return out
 
@@ -811,8 +804,8 @@ def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torc
     torch reductions compose the same numbers."""
     from statistics import NormalDist
     what = "modwt_wcorr"
-    level = _mra_level(level, what)
-    lo, hi = _mra_taps(dec_lo, dec_hi, what)
+    level = _int_level(level, 1, MRA_MAX_LEVEL, what)
+    lo, hi = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi)
     if boundary not in WCORR_BOUNDARY:
         raise ValueError(f"{what}: boundary must be one of {sorted(WCORR_BOUNDARY)}, got {boundary!r}")
     if not 0.0 < ci_level < 1.0:
@@ -820,23 +813,13 @@ def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torc
     if int(max_lag) != max_lag or max_lag < 0:
         raise ValueError(f"{what}: max_lag must be an integer >= 0, got {max_lag!r}")
     K = int(max_lag)
-    if y is None:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) \
-                or x.shape[-1] < 1:
-            raise ValueError(f"{what}: x must be float32 [n] or [batch, n] rows")
-        if K:
-            raise ValueError(f"{what}: max_lag needs a second series y")
-    else:
-        _ols_rows(x, y, what)
-    if K >= x.shape[-1]:
+    # the lag checks come before the operands': those end on the device
+    if K and y is None:
+        raise ValueError(f"{what}: max_lag needs a second series y")
+    if K and isinstance(x, torch.Tensor) and x.dim() and K >= x.shape[-1]:
         raise ValueError(f"{what}: max_lag must be below the series length {x.shape[-1]}, got {K}")
     z = NormalDist().inv_cdf(0.5 + 0.5 * ci_level)
-    if y is None:
-        dev = _check_dev(x)
-        x = _rows(x)
-    else:
-        dev = _check_dev(x, y)
-        x, y = _pair_rows(x, y)
+    dev, x, y = _series_or_pair(x, y, what, True)
     B, n = x.shape
     if n > (WCORR_MAX_LAG_N if K else WCORR_MAX_N) or lo.size > MRA_MAX_TAPS or K > WCORR_MAX_LAG:
         stats, xcorr = _wcorr_composed(x, y, lo, hi, level, K, boundary == "periodic", z)
@@ -844,8 +827,8 @@ def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torc
     stats = torch.empty((B, level, 8), dtype=torch.float64, device=dev)
     xcorr = torch.empty((B, level, 2 * K + 1), dtype=torch.float64, device=dev) if K else None
     with torch.cuda.device(dev):
-        _lib.call("wtmi_modwt_wcorr", _ptr(x), _ptr(y), x.stride(0), B, n, lo.ctypes.data_as(VP),
-                  hi.ctypes.data_as(VP), lo.size, level, WCORR_BOUNDARY[boundary], K, C.c_double(z),
+        _lib.call("wtmi_modwt_wcorr", _ptr(x), _ptr(y), x.stride(0), B, n, _tp(lo), _tp(hi),
+                  lo.size, level, WCORR_BOUNDARY[boundary], K, C.c_double(z),
                   _ptr(stats), _ptr(xcorr), _stream(dev))
     return {"stats": stats, "xcorr": xcorr}
 
@@ -856,13 +839,16 @@ def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torc
 def _register():
     lib = torch.library
 
+    def _batch(x, nd=2):
+        return x.shape[0] if x.dim() == nd else 1
+
     @lib.custom_op("wtmi::cwt", mutates_args=())
     def _cwt(x: torch.Tensor, scales: torch.Tensor, dt: float, f0: float) -> torch.Tensor:
         return cwt_morlet(x, scales, dt, f0)["w"]
 
     @_cwt.register_fake
     def _(x, scales, dt, f0):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, scales.numel(), x.shape[-1]),
+        return x.new_empty((_batch(x), scales.numel(), x.shape[-1]),
                            dtype=torch.complex64)
 
     @lib.custom_op("wtmi::cwt_power", mutates_args=())
@@ -871,7 +857,7 @@ def _register():
 
     @_cwt_power.register_fake
     def _(x, scales, dt, f0):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, scales.numel(), x.shape[-1]),
+        return x.new_empty((_batch(x), scales.numel(), x.shape[-1]),
                            dtype=torch.float32)
 
     @lib.custom_op("wtmi::wct", mutates_args=())
@@ -881,7 +867,7 @@ def _register():
 
     @_wct.register_fake
     def _(x1, x2, scales, dt, f0, boxcar):
-        return x1.new_empty((x1.shape[0] if x1.dim() == 2 else 1, scales.numel(), x1.shape[-1]),
+        return x1.new_empty((_batch(x1), scales.numel(), x1.shape[-1]),
                             dtype=torch.float32)
 
     @lib.custom_op("wtmi::modwt", mutates_args=())
@@ -891,7 +877,7 @@ def _register():
 
     @_modwt.register_fake
     def _(x, dec_lo, dec_hi, level):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level + 1, x.shape[-1]),
+        return x.new_empty((_batch(x), level + 1, x.shape[-1]),
                            dtype=torch.float32)
 
     @lib.custom_op("wtmi::imodwt", mutates_args=())
@@ -900,10 +886,10 @@ def _register():
 
     @_imodwt.register_fake
     def _(w, dec_lo, dec_hi):
-        return w.new_empty((w.shape[0] if w.dim() == 3 else 1, w.shape[-1]), dtype=torch.float32)
+        return w.new_empty((_batch(w, 3), w.shape[-1]), dtype=torch.float32)
 
     def _bs(x, scales, dtype):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, scales.numel(), x.shape[-1]),
+        return x.new_empty((_batch(x), scales.numel(), x.shape[-1]),
                            dtype=dtype)
 
     @lib.custom_op("wtmi::xwt", mutates_args=())
@@ -934,7 +920,7 @@ def _register():
     @_dwt.register_fake
     def _(x, dec_lo, dec_hi, level):
         total = sum(dwt_lengths(x.shape[-1], dec_lo.numel(), level))
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, total), dtype=torch.float32)
+        return x.new_empty((_batch(x), total), dtype=torch.float32)
 
     @lib.custom_op("wtmi::idwt", mutates_args=())
     def _idwt(coeffs: torch.Tensor, n: int, rec_lo: torch.Tensor, rec_hi: torch.Tensor,
@@ -947,7 +933,7 @@ def _register():
     def _(coeffs, n, rec_lo, rec_hi, level):
         lens = dwt_lengths(n, rec_lo.numel(), level)
         out_len = 2 * lens[-1] - rec_lo.numel() + 2 if level > 0 else n
-        return coeffs.new_empty((coeffs.shape[0] if coeffs.dim() == 2 else 1, out_len),
+        return coeffs.new_empty((_batch(coeffs), out_len),
                                 dtype=torch.float32)
 
     @lib.custom_op("wtmi::dwt_tsr", mutates_args=())
@@ -960,7 +946,7 @@ def _register():
 
     @_dwt_tsr.register_fake
     def _(x, y, dec_lo, dec_hi, rec_lo, rec_hi, level, add_constant):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level + 1, 8), dtype=torch.float64)
+        return x.new_empty((_batch(x), level + 1, 8), dtype=torch.float64)
 
     @lib.custom_op("wtmi::rows_ols", mutates_args=())
     def _rows_ols(x: torch.Tensor, y: torch.Tensor, add_constant: bool) -> torch.Tensor:
@@ -968,7 +954,7 @@ def _register():
 
     @_rows_ols.register_fake
     def _(x, y, add_constant):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, 8), dtype=torch.float64)
+        return x.new_empty((_batch(x), 8), dtype=torch.float64)
 
     @lib.custom_op("wtmi::dwt_smooth", mutates_args=())
     def _dwt_smooth(x: torch.Tensor, dec_lo: torch.Tensor, rec_lo: torch.Tensor, level: int
@@ -978,7 +964,7 @@ def _register():
 
     @_dwt_smooth.register_fake
     def _(x, dec_lo, rec_lo, level):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level, x.shape[-1]), dtype=torch.float32)
+        return x.new_empty((_batch(x), level, x.shape[-1]), dtype=torch.float32)
 
     @lib.custom_op("wtmi::modwt_mra", mutates_args=())
     def _modwt_mra(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, level: int
@@ -988,7 +974,7 @@ def _register():
 
     @_modwt_mra.register_fake
     def _(x, dec_lo, dec_hi, level):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level + 1, x.shape[-1]),
+        return x.new_empty((_batch(x), level + 1, x.shape[-1]),
                            dtype=torch.float32)
 
     @lib.custom_op("wtmi::modwt_mra_rows", mutates_args=())
@@ -997,7 +983,7 @@ def _register():
 
     @_modwt_mra_rows.register_fake
     def _(w, dec_lo, dec_hi):
-        return w.new_empty((w.shape[0] if w.dim() == 3 else 1, w.shape[-2], w.shape[-1]),
+        return w.new_empty((_batch(w, 3), w.shape[-2], w.shape[-1]),
                            dtype=torch.float32)
 
     @lib.custom_op("wtmi::modwt_wcorr", mutates_args=())
@@ -1009,7 +995,7 @@ def _register():
 
     @_modwt_wcorr.register_fake
     def _(x, y, dec_lo, dec_hi, level, periodic):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, level, 8), dtype=torch.float64)
+        return x.new_empty((_batch(x), level, 8), dtype=torch.float64)
 
     @lib.custom_op("wtmi::series_stats", mutates_args=())
     def _series_stats(x: torch.Tensor) -> torch.Tensor:
@@ -1018,7 +1004,7 @@ def _register():
 
     @_series_stats.register_fake
     def _(x):
-        return x.new_empty((x.shape[0] if x.dim() == 2 else 1, 8), dtype=torch.float64)
+        return x.new_empty((_batch(x), 8), dtype=torch.float64)
 
 
 try:
