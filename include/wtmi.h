@@ -225,6 +225,41 @@ int wtmi_dwt_smooth(const float* x, const float* y, long long ld, long long batc
                     const double* dec_lo, const double* rec_lo, int n_taps, int level,
                     int add_constant, float* smooth, double* stats, void* stream);
 
+/* ---- DWT wavelet shrinkage with MAD thresholds (K23) ---------------------------------
+ * Denoising by wavelet shrinkage (Donoho & Johnstone 1994) in one launch: pywt.wavedec (mode
+ * symmetric) of every series, a threshold per detail level, pywt.threshold of the detail
+ * arrays and pywt.waverec of the shrunk list.  cA_J is never modified.
+ * x: [batch][ld] float32; dec_* / rec_*: HOST pointers to the n_taps filters.
+ * rule 0 (fixed): lambda_j = thresholds[b * thr_ld + j - 1], DEVICE float64; thr_ld = 0: one
+ *   [level] row for every series, else thr_ld >= level.  mult is ignored, sigma_j is NaN.
+ * rule 1 (universal, VisuShrink): sigma = median(|cD_1|) / 0.6744897501960817 and lambda_j =
+ *   mult sigma sqrt(2 ln n) for every j, n the series length.
+ * rule 2 (level-dependent universal, Johnstone & Silverman 1997, for coloured noise):
+ *   sigma_j = median(|cD_j|) / 0.6744897501960817, lambda_j = mult sigma_j sqrt(2 ln n).
+ *   The median is np.median of the fp32 coefficients' magnitudes, exactly (the middle order
+ *   statistic, or the fp64 mean of the two middle ones; ties handled).  sigma and lambda are
+ *   fp64; a coefficient is compared in fp32 against (float)lambda.
+ * shrink 0 (soft): sign(c) max(|c| - lambda, 0).  shrink 1 (hard): c if |c| >= lambda, else 0.
+ * shrink 2 (non-negative garrote): c (1 - lambda^2 / c^2) if |c| > lambda, else 0 (lambda = 0
+ *   is the identity: 0 / 0 is never evaluated).
+ * out: [batch][ld_out] float32, the FIRST n samples of the reconstruction (pywt's
+ *   waverec(...)[:n]; not trim_signal, which drops sample 0 for odd n).  lambda = 0 returns x.
+ * info: NULL, or [batch][level][4] float64, row j-1 = sigma_j, lambda_j, kept_j, len_j; kept_j
+ *   counts the coefficients of cD_j that are non-zero by the rule's own inequality.
+ * coeffs: NULL, or [batch][total] float32, the shrunk coefficients in wtmi_wavedec's layout.
+ * -1: a NULL bank pointer or NULL out, ld < n, ld_out < n, level < 1, rule or shrink outside
+ *   0..2, mult < 0 or not finite, rule 0 without thresholds or with 0 < thr_ld < level.
+ * -2: n > 8192, n_taps odd or > 40, level > 60 (compose wtmi_wavedec, a shrink of the
+ *   coefficient rows and wtmi_waverec).  A level deeper than the series supports is exact.
+ *   Non-finite input samples are unspecified.
+ * One workgroup per series; every detail array stays in LDS between analysis and synthesis,
+ * about 2 n floats, so two workgroups share a CU up to n = 8192 (csrc/dwt_denoise.hip).    */
+int wtmi_dwt_denoise(const float* x, long long ld, long long batch, long long n,
+                     const double* dec_lo, const double* dec_hi, const double* rec_lo,
+                     const double* rec_hi, int n_taps, int level, int rule, int shrink, double mult,
+                     const double* thresholds, long long thr_ld, float* out, long long ld_out,
+                     double* info, float* coeffs, void* stream);
+
 /* ---- MODWT multiresolution analysis (K19 / K20) -------------------------------------
  * wtmi_modwt_mra replaces the MODWT workflow of src/modwt.py:466-487 in one launch: modwt
  * (:126-144) + modwtmra (:163-194) of x (and of y), smooth_signal (:232-251) and

@@ -159,6 +159,28 @@ def smooth_signal_batch(dwt_data_list: List[DataForDWT]) -> List[Dict[int, Dict[
     return out
 
 
+def denoise_signal_batch(dwt_data_list: List[DataForDWT], rule: str = "universal", shrink: str = "soft",
+                         mult: float = 1.0) -> List[Dict[str, npt.NDArray]]:
+    """Wavelet shrinkage of many series (engine extension; the reference only drops whole levels):
+    per entry {"signal": the denoised series, "sigma", "threshold", "kept": one value per detail
+    level 1 .. levels} (``levels=None``: pywt's maximum level).  rule "universal" or "level",
+    shrink "soft", "hard" or "garrote", as ``wtmi.transforms.dwt_denoise``.  Entries of one
+    (length, wavelet, level) share ONE fused launch."""
+    out: list = [None] * len(dwt_data_list)
+    groups: dict = {}
+    for i, d in enumerate(dwt_data_list):
+        w = as_filter_bank(d.mother_wavelet)
+        level = d.levels if d.levels is not None else max(1, transforms.dwt_max_level(len(d.y_values), w.dec_len))
+        groups.setdefault((len(d.y_values), w.name, tuple(w.dec_lo), level), []).append(i)
+    for (_, _, _, level), idx in groups.items():
+        w = as_filter_bank(dwt_data_list[idx[0]].mother_wavelet)
+        rows = np.stack([np.asarray(dwt_data_list[i].y_values, dtype=np.float64) for i in idx])
+        sig, info = transforms.dwt_denoise(rows, w, level, rule, shrink, mult, return_info=True)
+        for k, s, t in zip(idx, sig, info):
+            out[k] = {"signal": s, "sigma": t[:, 0], "threshold": t[:, 1], "kept": t[:, 2].astype(np.int64)}
+    return out
+
+
 def wavelet_approximation_batch(pairs, levels: int, mother_wavelet, add_constant: bool = True
                                 ) -> List[transforms.TimeScaleOLS]:
     """The fits of the reference's ``wavelet_approximation`` (src/regression.py:66-88) for many

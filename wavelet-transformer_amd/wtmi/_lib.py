@@ -52,6 +52,8 @@ PROTOTYPES = {
     "wtmi_dwt_tsr": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "wtmi_rows_ols": (_I32, [_P, _P, _I64, _I64, _I64, _I32, _P, _P]),
     "wtmi_dwt_smooth": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "wtmi_dwt_denoise": (_I32, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F64, _P, _I64,
+                                _P, _I64, _P, _P, _P]),
     "wtmi_modwt_mra": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "wtmi_modwt_mra_rows": (_I32, [_P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
     "wtmi_modwt_wcorr": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _F64, _P, _P, _P]),

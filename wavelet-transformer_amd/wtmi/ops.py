@@ -675,8 +675,103 @@ def dwt_smooth(x: torch.Tensor, dec_lo, rec_lo, level: int, *, y: Optional[torch
     return {"smooth": smooth, "stats": stats}
 
 
+# ----------------------------------------------------------- wavelet shrinkage
+DENOISE_RULES = {"fixed": 0, "universal": 1, "level": 2}
+DENOISE_SHRINK = {"soft": 0, "hard": 1, "garrote": 2}
+DENOISE_INFO = ("sigma", "threshold", "kept", "len")
+MAD_SCALE = 0.6744897501960817  # the normal distribution's upper quartile: sigma = MAD / this
+
+
+def _denoise_composed(x, taps, level, rule, shrink, mult, thr):
+    """The numbers of wtmi_dwt_denoise from wavedec, torch order statistics and ``where`` per
+    level, and waverec: (denoised [B, n], info [B, level, 4], shrunk coeffs [B, total])."""
+    B, n = x.shape
+    coeffs, lens = wavedec(x, taps[0], taps[1], level)
+    info = torch.full((B, level, 4), float("nan"), dtype=torch.float64, device=x.device)
+    scale = mult * float(np.sqrt(2.0 * np.log(n)))
+    end, sigma = coeffs.shape[1], None
+    for j in range(1, level + 1):  # cD_j is list entry level + 1 - j: the arrays run backwards
+        m = lens[level + 1 - j]
+        c = coeffs[:, end - m:end]
+        end -= m
+        mag = c.abs()
+        if rule == 0:
+            lam = thr[:, j - 1]
+        else:
+            if rule == 2 or j == 1:
+                s = torch.sort(mag, dim=1).values[:, [(m - 1) // 2, m // 2]].to(torch.float64)
+                sigma = 0.5 * (s[:, 0] + s[:, 1]) / MAD_SCALE
+            lam = scale * sigma
+            info[:, j - 1, 0] = sigma
+        lf = lam.to(torch.float32)[:, None]
+        keep = mag >= lf if shrink == 1 else mag > lf
+        if shrink == 0:
+            val = torch.copysign(mag - lf, c)
+        elif shrink == 1:
+            val = c
+        else:
+            val = c - lf * (lf / torch.where(keep, c, torch.ones_like(c)))
+        c.copy_(torch.where(keep, val, torch.zeros_like(c)))
+        info[:, j - 1, 1] = lam
+        info[:, j - 1, 2] = keep.sum(dim=1)
+        info[:, j - 1, 3] = m
+    rec = waverec(coeffs, n, taps[2], taps[3], level, [(1 << (level + 1)) - 1])
+    return rec[:, 0, :n].contiguous(), info, coeffs
+
+
+def dwt_denoise(x: torch.Tensor, dec_lo, dec_hi, rec_lo, rec_hi, level: int, *, rule: str = "universal",
+                shrink: str = "soft", mult: float = 1.0, thresholds=None, want_info: bool = True,
+                want_coeffs: bool = False):
+    """Wavelet shrinkage of float32 rows x ([n] or [B, n]): wavedec (mode symmetric), a threshold
+    per detail level, pywt.threshold of the detail arrays and the first n samples of waverec:
+    {"denoised": [B, n] float32, "info": [B, level, 4] float64 (``DENOISE_INFO``, row j - 1 =
+    level j) or None, "coeffs": [B, total] float32 (the shrunk list, wavedec's layout) or None}.
+    rule "universal": lambda = mult sigma sqrt(2 ln n) with sigma = median(|cD_1|) / ``MAD_SCALE``;
+    "level": the same with sigma_j from cD_j; "fixed": ``thresholds`` ([level] or [B, level],
+    float64) and mult ignored.  shrink: "soft", "hard" or "garrote" (non-negative garrote).  Rows
+    of at most ``TSR_MAX_N`` samples, even filters of at most ``TSR_MAX_TAPS`` taps and levels up
+    to ``SMOOTH_MAX_LEVEL`` take ONE fused launch (wtmi_dwt_denoise); beyond, wavedec, torch order
+    statistics and waverec compose the same numbers."""
+    what = "dwt_denoise"
+    level = _int_level(level, 1, None, what)
+    taps = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi, rec_lo=rec_lo, rec_hi=rec_hi)
+    if rule not in DENOISE_RULES:
+        raise ValueError(f"{what}: rule must be one of {sorted(DENOISE_RULES)}, got {rule!r}")
+    if shrink not in DENOISE_SHRINK:
+        raise ValueError(f"{what}: shrink must be one of {sorted(DENOISE_SHRINK)}, got {shrink!r}")
+    mult = float(mult)
+    if not (mult >= 0.0 and np.isfinite(mult)):
+        raise ValueError(f"{what}: mult must be finite and >= 0, got {mult!r}")
+    fixed = rule == "fixed"
+    if fixed != (thresholds is not None):
+        raise ValueError(f"{what}: thresholds go with rule 'fixed' and with no other")
+    if fixed and (len(_shape(thresholds)) not in (1, 2) or _shape(thresholds)[-1] != level):
+        raise ValueError(f"{what}: thresholds must be [{level}] or [batch, {level}], got shape "
+                         f"{_shape(thresholds)}")
+    dev, x, _ = _series_or_pair(x, None, what, True)
+    B, n = x.shape
+    thr = _f64_dev(thresholds, dev)
+    if fixed and thr.dim() == 2 and thr.shape[0] != B:
+        raise ValueError(f"{what}: {thr.shape[0]} threshold rows for {B} series")
+    F = taps[0].size
+    r, s = DENOISE_RULES[rule], DENOISE_SHRINK[shrink]
+    if n > TSR_MAX_N or F % 2 or F > TSR_MAX_TAPS or level > SMOOTH_MAX_LEVEL:
+        den, info, coeffs = _denoise_composed(x, taps, level, r, s, mult,
+                                              thr.reshape(-1, level).expand(B, level) if fixed else None)
+        return {"denoised": den, "info": info if want_info else None, "coeffs": coeffs if want_coeffs else None}
+    den = torch.empty((B, n), dtype=torch.float32, device=dev)
+    info = torch.empty((B, level, 4), dtype=torch.float64, device=dev) if want_info else None
+    coeffs = torch.empty((B, sum(dwt_lengths(n, F, level))), dtype=torch.float32, device=dev) \
+        if want_coeffs else None
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_dwt_denoise", _ptr(x), x.stride(0), B, n, *map(_tp, taps), F, level, r, s,
+                  C.c_double(mult), _ptr(thr), level if fixed and thr.dim() == 2 else 0,
+                  _ptr(den), n, _ptr(info), _ptr(coeffs), _stream(dev))
+    return {"denoised": den, "info": info, "coeffs": coeffs}
+
+
 # ------------------------------------------------------------------- MODWT MRA
-MRA_MAX_N = 16384   # longest row of the fused kernels (include/wtmi.h: wtmi_modwt_mra)
+MRA_MAX_N = 16384  # longest row of the fused kernels (include/wtmi.h: wtmi_modwt_mra)
 MRA_MAX_TAPS = 40
 MRA_MAX_LEVEL = 62  # the a-trous dilation 2^(level - 1) as a long long (wtmi_modwt_mra, _rows, wtmi_modwt_wcorr)
 
@@ -965,6 +1060,17 @@ def _register():
     @_dwt_smooth.register_fake
     def _(x, dec_lo, rec_lo, level):
         return x.new_empty((_batch(x), level, x.shape[-1]), dtype=torch.float32)
+
+    @lib.custom_op("wtmi::dwt_denoise", mutates_args=())
+    def _dwt_denoise(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, rec_lo: torch.Tensor,
+                     rec_hi: torch.Tensor, level: int, rule: str, shrink: str, mult: float) -> torch.Tensor:
+        """Wavelet shrinkage with a MAD threshold (rule "universal" or "level"): [B, n]."""
+        banks = [t.cpu().numpy() for t in (dec_lo, dec_hi, rec_lo, rec_hi)]
+        return dwt_denoise(x, *banks, level, rule=rule, shrink=shrink, mult=mult, want_info=False)["denoised"]
+
+    @_dwt_denoise.register_fake
+    def _(x, dec_lo, dec_hi, rec_lo, rec_hi, level, rule, shrink, mult):
+        return x.new_empty((_batch(x), x.shape[-1]), dtype=torch.float32)
 
     @lib.custom_op("wtmi::modwt_mra", mutates_args=())
     def _modwt_mra(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, level: int

@@ -689,6 +689,26 @@ def dwt_smooth(data, wavelet, level=None):
     return out[0] if a.ndim == 1 else out
 
 
+def dwt_denoise(data, wavelet, level=None, rule="universal", shrink="soft", mult=1.0, thresholds=None,
+                return_info=False):
+    """Wavelet shrinkage of an [n] series (or a [B, n] batch) in one fused launch: fp64 samples of
+    the same shape.  rule / shrink / mult / thresholds as ``ops.dwt_denoise``; level=None:
+    ``dwt_max_level`` (at least 1).  return_info: also the fp64 [level, 4] table (``[B, level, 4]``
+    for a batch) of sigma, threshold, kept and length per detail level."""
+    w = as_filter_bank(wavelet)
+    a = np.asarray(data)
+    if level is None:
+        level = max(1, dwt_max_level(a.shape[-1], w.dec_len))
+    res = ops.dwt_denoise(_to_dev(a, torch.float32), w.dec_lo, w.dec_hi, w.rec_lo, w.rec_hi, int(level),
+                          rule=rule, shrink=shrink, mult=mult, thresholds=thresholds, want_info=return_info)
+    out = _np(res["denoised"], np.float64)
+    out = out[0] if a.ndim == 1 else out
+    if not return_info:
+        return out
+    info = _np(res["info"], np.float64)
+    return out, (info[0] if a.ndim == 1 else info)
+
+
 def wavelet_approximation(input_data, output_data, levels: int, wavelet, add_constant: bool = True):
     """``wavelet_approximation`` of src/regression.py:66-88 on the smooths of ``input_data``: the
     raw output series regressed on each smooth, crystals c = 1 .. levels (the reference dict's
