@@ -70,6 +70,33 @@ int wtmi_xwt_mother(const float* x1, const float* x2, long long ld, long long ba
  * 1 GiB each).  Rows up to 2^20 samples; longer ones return kErrUnsupported.         */
 long long wtmi_cwt_workspace_bytes(long long batch, long long n0, int n_scales, int pair);
 
+/* ---- CWT summaries (K24) ---------------------------------------------------------
+ * Three reductions of the [batch][n_scales][n0] transform of wtmi_cwt_mother in one launch,
+ * with that array neither written nor read:
+ *   out_global [batch][n_scales]: mean over t in [t_lo[j], t_hi[j]) (clipped to [0, n0); both
+ *     NULL: the whole row; an empty range gives NaN) of |W_j(t)|^2 -- replaces
+ *     power.mean(axis=1), the global wavelet spectrum;
+ *   out_band_power [batch][n_bands][n0] = sum_j power_w[k][j] |W_j(t)|^2 -- the scale-averaged
+ *     power of Torrence & Compo 1998 eq. 24 with power_w = dj dt / (Cdelta s_j) inside band k;
+ *   out_band_signal [batch][n_bands][n0] = sum_j signal_w[k][j] Re W_j(t) -- eq. 11 / pycwt.icwt
+ *     restricted to band k with signal_w = dj sqrt(dt) / (Cdelta psi_0(0) sqrt(s_j)).
+ * power_w / signal_w: float64 [n_bands][n_scales] device arrays, zero outside a band; n_bands in
+ * 0..4.  Any output may be NULL, not all; a band output needs its weights and n_bands >= 1.
+ * out_band_signal alone costs n_bands inverse transforms (the band-pass filter), not n_scales.
+ * n0 in 9..16384 (band power: up to 8192); other lengths return -2 (compose them from
+ * wtmi_cwt_mother).  workspace: wtmi_cwt_summary_workspace_bytes bytes when that is non-zero
+ * (partial rows of series split over several workgroups; NULL then returns -1).  That size is
+ * non-decreasing in n_bands, and in batch only while a series is split: it falls to 0 once every
+ * series is one chunk (512 series or more with at most 128 scales, 64 from 8193 samples), so a
+ * buffer kept for several batch sizes takes the largest value over them, not the value at the
+ * largest batch.  No floating-point atomics: equal inputs give equal bits.                  */
+int wtmi_cwt_summary(const float* x, long long ld, long long batch, long long n0,
+                     const double* affine, const double* scales, int n_scales, double dt,
+                     int mother, double param, const int* t_lo, const int* t_hi, int n_bands,
+                     const double* power_w, const double* signal_w, float* out_global,
+                     float* out_band_power, float* out_band_signal, void* workspace, void* stream);
+long long wtmi_cwt_summary_workspace_bytes(long long batch, long long n0, int n_scales, int n_bands);
+
 /* ---- XWT / phase (K1+K2, pair mode) ------------------------------------------
  * Replaces the two pycwt.cwt calls and W1*conj(W2) inside pycwt.xwt
  * (src/xwt.py:93-101) and the phase angle(W12) of pycwt.wct used for the arrows

@@ -351,5 +351,55 @@ __device__ __forceinline__ cpx morlet_bin0(cpx X0, cpx prm, float f0, int t) {
   return cscale(X0, __builtin_amdgcn_exp2f(fmaf(e * K, e, prm.y)));
 }
 
+// W row of one scale: Morlet filter + inverse FFT, entering the FFT at pass q when the
+// filtered spectrum is confined to bins [0, N/16^q) (band_regime / band_entry), with the
+// entry pass narrowed to its NZ non-zero inputs (row_code).
+template <int LOGN, int NBUF, bool TWL, int Q, int NZ>
+__device__ __forceinline__ void inverse_row_v(cpx (&v)[16], const cpx (&X)[16], cpx prm, float f0,
+                                              cpx* my, int bufstride, const cpx* tw, int t, int& par,
+                                              const float4* twl) {
+  if constexpr (Q == 0) {
+    if constexpr (NZ < 16)
+      morlet_filter_nz<LOGN, NZ>(v, X, prm, f0, t);
+    else
+      morlet_filter<LOGN>(v, X, prm, f0, t);
+    fft_row<LOGN, 1, NBUF, TWL, 0, NZ>(v, my, bufstride, tw, t, par, twl);
+  } else {
+    band_entry<LOGN, Q, NZ>(v, morlet_bin0(X[0], prm, f0, t), my, t);
+    fft_row<LOGN, 1, NBUF, TWL, Q, NZ>(v, my, bufstride, tw, t, par, twl);
+  }
+}
+
+template <int LOGN, int NBUF, bool TWL>
+__device__ __forceinline__ void inverse_row(cpx (&v)[16], const cpx (&X)[16], cpx prm, float f0,
+                                            int code, cpx* my, int bufstride, const cpx* tw, int t,
+                                            int& par, const float4* twl) {
+  using P = FftPlan<LOGN>;
+#define WTMI_ROW(Q, NZ) inverse_row_v<LOGN, NBUF, TWL, Q, NZ>(v, X, prm, f0, my, bufstride, tw, t, par, twl)
+  if constexpr (NBUF == 1 && P::P16 >= 2 && (P::NT % 16) == 0) {
+    switch (code) {
+      case 1: WTMI_ROW(0, 8); return;
+      case 2: WTMI_ROW(0, 4); return;
+      case 3: WTMI_ROW(0, 2); return;
+      case 4: WTMI_ROW(1, 16); return;
+      case 5: WTMI_ROW(1, 8); return;
+      case 6: WTMI_ROW(1, 4); return;
+      case 7: WTMI_ROW(1, 2); return;
+      default: break;
+    }
+    if constexpr (P::P16 >= 3 && (P::NT % 256) == 0) {
+      switch (code) {
+        case 8: WTMI_ROW(2, 16); return;
+        case 9: WTMI_ROW(2, 8); return;
+        case 10: WTMI_ROW(2, 4); return;
+        case 11: WTMI_ROW(2, 2); return;
+        default: break;
+      }
+    }
+  }
+  WTMI_ROW(0, 16);
+#undef WTMI_ROW
+}
+
 }  // inline namespace WTMI_FFT_NS
 }  // namespace wtmi

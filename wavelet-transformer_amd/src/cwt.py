@@ -126,6 +126,37 @@ def run_cwt_batch(cwt_data_list: List[DataForCWT], normalize: bool = True,
     return out
 
 
+def summarize_cwt_batch(cwt_data_list: List[DataForCWT], bands, coi: bool = False,
+                        standardize: bool = False, **kwargs) -> List[transforms.CwtSummary]:
+    """Global wavelet spectrum, scale-averaged power and band-pass reconstruction of many series in
+    the period bands ``bands`` = [(pmin, pmax), ...] (engine extension beside ``run_cwt_batch``:
+    same module constants, same standardisation, here as the kernel's affine operand).  Series of
+    one length and mother share ONE fused launch (ops.cwt_summary); no power array is made.
+    Rounding order: the series is rounded to fp32 and the kernel's load standardises it in fp64,
+    where ``run_cwt_batch`` standardises the fp64 series and rounds the result; for a series whose
+    offset is large against its spread the two inputs differ by the fp32 rounding of the offset."""
+    out: List[transforms.CwtSummary] = [None] * len(cwt_data_list)
+    groups: dict = {}
+    for i, d in enumerate(cwt_data_list):
+        groups.setdefault((np.asarray(d.y_values).size, kernel_mother(d.mother_wavelet)), []).append(i)
+    for (n0, _), idx in groups.items():
+        mother = as_mother(cwt_data_list[idx[0]].mother_wavelet)
+        y = transforms._to_dev(np.stack([np.asarray(cwt_data_list[i].y_values, dtype=np.float64)
+                                         for i in idx]))
+        coef = transforms.standardize_coefs(ops.series_moments(y), **kwargs) if standardize else None
+        sj, freqs = transforms.scales_for(n0, DT, DJ, S0, J, mother)
+        pw, rw = transforms.band_weights(sj, DT, DJ, mother, bands) if len(bands) else (None, None)
+        res = ops.cwt_summary(y.to(torch.float32), sj, DT, mother=mother, affine=coef,
+                              t_range=transforms.coi_ranges(n0, DT, sj, mother) if coi else None,
+                              power_weights=pw, signal_weights=rw)
+        g, bp, bs = (None if res[k] is None else transforms._np(res[k])
+                     for k in ("global_power", "band_power", "band_signal"))
+        for k, i in enumerate(idx):
+            out[i] = transforms.CwtSummary(g[k], None if bp is None else bp[k], None if bs is None else bs[k],
+                                           sj, 1 / freqs, freqs)
+    return out
+
+
 def plot_cwt(cwt_ax, cwt_data: Type[DataForCWT], cwt_results: Type[ResultsFromCWT],
              include_significance: bool = True, include_cone_of_influence: bool = True,
              **kwargs) -> None:

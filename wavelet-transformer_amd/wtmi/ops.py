@@ -244,6 +244,105 @@ def cwt_morlet(x: torch.Tensor, scales, dt: float, f0: float = 6.0, *,
     return res
 
 
+SUMMARY_MAX_BANDS = 4      # include/wtmi.h: wtmi_cwt_summary
+SUMMARY_MIN_N, SUMMARY_MAX_N = 9, 16384  # rows of the fused kernel; beyond, the composed path
+SUMMARY_MAX_POWER_N = 8192  # band power rides on the scale loop's registers up to N = 8192
+
+
+def _summary_composed(x, scales, dt, f0, mother, affine, lo, hi, pw, rw, want_global):
+    """The numbers of wtmi_cwt_summary from ops.cwt_morlet over slabs of scales and fp64 torch
+    reductions (rows the fused kernel does not take), in the fused path's layout and dtypes."""
+    B, n0 = x.shape
+    sc = np.asarray(scales.cpu() if isinstance(scales, torch.Tensor) else scales, dtype=np.float64)
+    S, dev = sc.size, x.device
+    slab = max(1, min(S, (1 << 28) // max(1, 16 * B * n0)))
+    glob = torch.empty((B, S), dtype=torch.float64, device=dev) if want_global else None
+    bp = None if pw is None else torch.zeros((B, pw.shape[0], n0), dtype=torch.float64, device=dev)
+    bs = None if rw is None else torch.zeros((B, rw.shape[0], n0), dtype=torch.float64, device=dev)
+    tpos = torch.arange(n0, device=dev)
+    for j0 in range(0, S, slab):
+        j1 = min(S, j0 + slab)
+        W = cwt_morlet(x, sc[j0:j1], dt, f0, affine=affine, mother=mother)["w"].to(torch.complex128)
+        P = W.real ** 2 + W.imag ** 2
+        if want_global:
+            m = (tpos[None, :] >= lo[j0:j1, None]) & (tpos[None, :] < hi[j0:j1, None])
+            glob[:, j0:j1] = (P * m).sum(-1) / m.sum(-1)  # an empty range: 0 / 0 = NaN
+        if bp is not None:
+            bp += torch.einsum("kj,bjt->bkt", pw[:, j0:j1], P)
+        if bs is not None:
+            bs += torch.einsum("kj,bjt->bkt", rw[:, j0:j1], W.real)
+    return tuple(None if t is None else t.to(torch.float32) for t in (glob, bp, bs))
+
+
+def cwt_summary(x: torch.Tensor, scales, dt: float, f0: float = 6.0, *, mother=None,
+                affine: Optional[torch.Tensor] = None, t_range=None, power_weights=None,
+                signal_weights=None, want_global: bool = True):
+    """Summaries of the CWT of every row of x (float32 [B, n0]) with no [B, S, n0] array written:
+    {"global_power": [B, S] mean over time of |W_j|^2 (t_range = (t_lo, t_hi), int [S] each: the
+    mean over [t_lo[j], t_hi[j]) only, NaN for an empty range), "band_power": [B, K, n0] =
+    sum_j power_weights[k, j] |W_j(t)|^2, "band_signal": [B, K, n0] = sum_j signal_weights[k, j]
+    Re W_j(t)}, float32, None for what was not asked.  Weights are [K, S] with K <=
+    ``SUMMARY_MAX_BANDS`` (transforms.band_weights makes Torrence & Compo's eq. 24 / eq. 11 rows).
+    One fused launch (wtmi_cwt_summary) for rows of ``SUMMARY_MIN_N`` .. ``SUMMARY_MAX_N`` samples
+    (longer rows up to ``SUMMARY_MAX_N``: band power alone is composed, the global spectrum and the
+    band signal stay fused); other lengths run ops.cwt_morlet over slabs of scales and reduce in
+    fp64.  signal_weights alone is the band-pass filter: K inverse transforms, not S."""
+    what = "cwt_summary"
+    x = _rows(x)
+    B, n0 = x.shape
+    S = _n_scales(scales)
+    _check_affine(affine, B, "affine")
+    K = 0
+    for name, w in (("power_weights", power_weights), ("signal_weights", signal_weights)):
+        if w is None:
+            continue
+        shp = _shape(w)
+        if len(shp) != 2 or shp[1] != S or not 1 <= shp[0] <= SUMMARY_MAX_BANDS or (K and shp[0] != K):
+            raise ValueError(f"{what}: {name} must be [K, {S}] with 1 <= K <= {SUMMARY_MAX_BANDS} (one K for "
+                             f"both weight arrays), got shape {shp}")
+        K = shp[0]
+    if not (want_global or K):
+        raise ValueError(f"{what}: no output requested")
+    if t_range is not None and (len(t_range) != 2 or _shape(t_range[0]) != (S,) or _shape(t_range[1]) != (S,)):
+        raise ValueError(f"{what}: t_range must be a (t_lo, t_hi) pair of [{S}] integer arrays")
+    dev = _check_dev(x, affine)
+    x = _rows(x, torch.float32)
+    mid, mpar = _mother_args(mother, f0)
+    if mid != 0 and n0 > 16384:
+        raise ValueError("non-Morlet mothers: series of at most 16384 samples")
+    aff = _f64_arg(affine, dev)
+    pw, rw = _f64_dev(power_weights, dev), _f64_dev(signal_weights, dev)
+    lo = hi = None
+    if t_range is not None and want_global:
+        lo, hi = (torch.as_tensor(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)).to(
+            device=dev, dtype=torch.int32).contiguous() for t in t_range)
+    keys = ("global_power", "band_power", "band_signal")
+    if not SUMMARY_MIN_N <= n0 <= SUMMARY_MAX_N:
+        if lo is None:
+            lo = torch.zeros(S, dtype=torch.int32, device=dev)
+            hi = torch.full((S,), n0, dtype=torch.int32, device=dev)
+        return dict(zip(keys, _summary_composed(x, scales, dt, f0, (mid, mpar), aff, lo.clamp(min=0),
+                                                hi.clamp(max=n0), pw, rw, want_global)))
+    bp = None
+    if pw is not None and n0 > SUMMARY_MAX_POWER_N:  # band power alone is composed at this length
+        bp = _summary_composed(x, scales, dt, f0, (mid, mpar), aff, None, None, pw, None, False)[1]
+        if not want_global and rw is None:
+            return dict(zip(keys, (None, bp, None)))
+        pw = None
+    sc = _f64_dev(scales, dev)
+    glob = torch.empty((B, S), dtype=torch.float32, device=dev) if want_global else None
+    if pw is not None:
+        bp = torch.empty((B, K, n0), dtype=torch.float32, device=dev)
+    bs = torch.empty((B, K, n0), dtype=torch.float32, device=dev) if rw is not None else None
+    need = int(_lib.call("wtmi_cwt_summary_workspace_bytes", B, n0, S, K))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need > 0 else None
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_cwt_summary", _ptr(x), x.stride(0), B, n0, _ptr(aff), _ptr(sc), S, float(dt), mid, mpar,
+                  _ptr(lo), _ptr(hi), K, _ptr(pw), _ptr(rw), _ptr(glob), _ptr(bp if pw is not None else None),
+                  _ptr(bs), _ptr(ws), _stream(dev))
+    return dict(zip(keys, (glob, bp, bs)))
+
+
 MAX_SAMPLES = 1 << 20  # longest row the engine transforms (include/wtmi.h)
 
 
@@ -954,6 +1053,19 @@ def _register():
     def _(x, scales, dt, f0):
         return x.new_empty((_batch(x), scales.numel(), x.shape[-1]),
                            dtype=torch.float32)
+
+    @lib.custom_op("wtmi::cwt_summary", mutates_args=())
+    def _cwt_summary(x: torch.Tensor, scales: torch.Tensor, dt: float, f0: float, power_weights: torch.Tensor,
+                     signal_weights: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Global spectrum [B, S], band power and band signal [B, K, n0] of Morlet(f0) transforms."""
+        r = cwt_summary(x, scales, dt, f0, power_weights=power_weights, signal_weights=signal_weights)
+        return r["global_power"], r["band_power"], r["band_signal"]
+
+    @_cwt_summary.register_fake
+    def _(x, scales, dt, f0, power_weights, signal_weights):
+        B, K, n = _batch(x), power_weights.shape[0], x.shape[-1]
+        return (x.new_empty((B, scales.numel()), dtype=torch.float32),
+                x.new_empty((B, K, n), dtype=torch.float32), x.new_empty((B, K, n), dtype=torch.float32))
 
     @lib.custom_op("wtmi::wct", mutates_args=())
     def _wct(x1: torch.Tensor, x2: torch.Tensor, scales: torch.Tensor, dt: float, f0: float,

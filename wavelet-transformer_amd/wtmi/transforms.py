@@ -204,6 +204,74 @@ def cwt(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None):
             _np(ft[1:N // 2]) / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
 
 
+def band_weights(sj, dt, dj, wavelet, bands):
+    """Weight rows of ops.cwt_summary for period bands [(pmin, pmax), ...] (both ends included,
+    selected on wavelet.flambda() * sj): (pw, rw), fp64 [K, S] each, with
+    pw[k, j] = dj dt / (Cdelta s_j) (scale-averaged power, Torrence & Compo 1998 eq. 24) and
+    rw[k, j] = dj sqrt(dt) / (Cdelta psi_0(0) sqrt(s_j)) (reconstruction, eq. 11) inside band k and
+    0 outside.  Raises for a mother without a reconstruction factor (cdelta = -1)."""
+    wavelet = as_mother(wavelet)
+    if wavelet.cdelta == -1 or not wavelet.psi0:
+        raise ValueError(f"{wavelet!r} has no reconstruction factor (cdelta = {wavelet.cdelta}, psi0 = "
+                         f"{wavelet.psi0:g})")
+    sj = np.asarray(sj, dtype=np.float64)
+    period = wavelet.flambda() * sj
+    inside = np.array([(period >= pmin) & (period <= pmax) for pmin, pmax in bands], dtype=bool).reshape(-1, sj.size)
+    pw = inside * (dj * dt / (wavelet.cdelta * sj))
+    rw = inside * (dj * np.sqrt(dt) / (wavelet.cdelta * wavelet.psi0 * np.sqrt(sj)))
+    return pw, rw
+
+
+def coi_ranges(n0: int, dt: float, sj, wavelet):
+    """Per scale the interval [t_lo, t_hi) of samples outside the cone of influence (period_j <=
+    coi_t; the cone is a triangle, so the set is an interval; (0, 0) where it is empty)."""
+    wavelet = as_mother(wavelet)
+    inside = (wavelet.flambda() * np.asarray(sj))[:, None] <= cone_of_influence(n0, dt, wavelet)[None, :]
+    some = inside.any(axis=1)
+    lo = np.where(some, inside.argmax(axis=1), 0).astype(np.int32)
+    hi = np.where(some, n0 - inside[:, ::-1].argmax(axis=1), 0).astype(np.int32)
+    return lo, hi
+
+
+@dataclass
+class CwtSummary:
+    """Reductions of one series' CWT (``cwt_summary``): global_power [S] (time mean of |W|^2),
+    band_power / band_signal [K, n0] per period band (T&C eq. 24 / eq. 11; None without bands)."""
+
+    global_power: np.ndarray
+    band_power: Optional[np.ndarray]
+    band_signal: Optional[np.ndarray]
+    scales: np.ndarray
+    periods: np.ndarray
+    freqs: np.ndarray
+
+
+def cwt_summary(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", bands=(), coi=False):
+    """Global wavelet spectrum, scale-averaged power and band-pass reconstruction of a series in
+    the period bands ``bands`` = [(pmin, pmax), ...], one fused launch and no [S, n0] array.
+    coi=True: the global spectrum averages each scale over the samples outside the cone of
+    influence only (NaN for a scale wholly inside it)."""
+    wavelet = as_mother(wavelet)
+    x = _to_dev(np.asarray(signal), torch.float32).reshape(1, -1)
+    n0 = x.shape[1]
+    sj, freqs = scales_for(n0, dt, dj, s0, J, wavelet)
+    pw, rw = band_weights(sj, dt, dj, wavelet, bands) if len(bands) else (None, None)
+    res = ops.cwt_summary(x, sj, dt, mother=wavelet, t_range=coi_ranges(n0, dt, sj, wavelet) if coi else None,
+                          power_weights=pw, signal_weights=rw)
+    bp, bs = (None if res[k] is None else _np(res[k][0]) for k in ("band_power", "band_signal"))
+    return CwtSummary(_np(res["global_power"][0]), bp, bs, sj, 1 / freqs, freqs)
+
+
+def cwt_bandpass(signal, dt, pmin, pmax, dj=1 / 12, s0=-1, J=-1, wavelet="morlet"):
+    """The series band-passed to periods [pmin, pmax] by the wavelet reconstruction (T&C eq. 11
+    over the band's scales): one inverse transform, no per-scale rows.  float32 [n0]."""
+    wavelet = as_mother(wavelet)
+    x = _to_dev(np.asarray(signal), torch.float32).reshape(1, -1)
+    sj, _ = scales_for(x.shape[1], dt, dj, s0, J, wavelet)
+    _, rw = band_weights(sj, dt, dj, wavelet, [(pmin, pmax)])
+    return _np(ops.cwt_summary(x, sj, dt, mother=wavelet, signal_weights=rw, want_global=False)["band_signal"][0, 0])
+
+
 # ----------------------------------------------------------------- XWT / WCT
 def _pair_norm(y1, y2):
     d1, d2 = _to_dev(y1).reshape(1, -1), _to_dev(y2).reshape(1, -1)

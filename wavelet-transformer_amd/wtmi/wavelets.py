@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import json
 import os
+from math import lgamma
 
 import numpy as np
 
@@ -31,6 +32,7 @@ class Morlet:
             self.cdelta, self.gamma, self.deltaj0 = 0.776, 2.32, 0.60
         else:
             self.cdelta = self.gamma = self.deltaj0 = -1
+        self.psi0 = np.pi ** -0.25  # psi_0(0), Torrence & Compo Table 2 (the reconstruction factor)
 
     def psi_ft(self, f):
         return (np.pi ** -0.25) * np.exp(-0.5 * (np.asarray(f) - self.f0) ** 2)
@@ -55,6 +57,8 @@ class Paul:
 
     def __init__(self, m: int = 4):
         self.m, self.dofmin = m, 2
+        # psi_0(0) = 2^m m! / sqrt(pi (2m)!) (T&C Table 2; 1.079 at m = 4)
+        self.psi0 = float(np.exp(m * np.log(2.0) + lgamma(m + 1) - 0.5 * (np.log(np.pi) + lgamma(2 * m + 1))))
         if m == 4:
             self.cdelta, self.gamma, self.deltaj0 = 1.132, 1.17, 1.5
         else:
@@ -86,6 +90,10 @@ class DOG:
 
     def __init__(self, m: int = 2):
         self.m, self.dofmin = m, 1
+        # psi_0(0) = (-1)^(m/2 + 1) (m - 1)!! / sqrt(Gamma(m + 1/2)) for even m (T&C Table 2: 0.867 at
+        # m = 2, 0.884 at m = 6), 0 for odd m (an odd wavelet: no real-part reconstruction)
+        self.psi0 = 0.0 if m % 2 else float((-1) ** (m // 2 + 1) * np.prod(np.arange(m - 1, 0, -2.0))
+                                            / np.sqrt(np.exp(lgamma(m + 0.5))))
         if m == 2:
             self.cdelta, self.gamma, self.deltaj0 = 3.541, 1.43, 1.4
         elif m == 6:
