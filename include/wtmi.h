@@ -344,6 +344,37 @@ int wtmi_modwt_wcorr(const float* x, const float* y, long long ld, long long bat
                      const double* dec_lo, const double* dec_hi, int n_taps, int level,
                      int boundary, int max_lag, double z, double* stats, double* xcorr, void* stream);
 
+/* ---- MODWT wavelet correlation matrix / wavelet multiple correlation (K25) -------------
+ * K22 for M series at once: the wavelet covariance and correlation matrices of all M series of a
+ * group at every MODWT detail level (the by-scale correlation_matrix_pvalues table itself) and
+ * the wavelet multiple correlation of Fernandez-Macho (2012; the R package wavemulcor), from the
+ * series themselves in one launch.  The per-level Gram matrix W_j W_j^T is accumulated by the
+ * fp64 16 x 16 x 4 matrix instruction in fp64 from the fp32 coefficients; W_j never leaves the
+ * registers.
+ * x: [batch][n_series][ld] float32 (M = n_series); the passes run on x - x[0] of every series.
+ * boundary, z, t0, M_j and n_eff as wtmi_modwt_wcorr.
+ * cov: [batch][level][M][M] float64, (1/M_j) sums over t >= t0 of W^a W^b, full and symmetric
+ *   bit for bit.  corr: NULL or the same shape, cov_ab / sqrt(cov_aa cov_bb), symmetric bit for
+ *   bit, the diagonal exactly 1 where the variance is not 0.
+ * r2: [batch][level][M], R^2_i = 1 - 1 / (P_j^-1)_ii of series i regressed on the others, P_j =
+ *   corr, from an fp64 Cholesky factor P = L L^T: (P^-1)_ii = sum_k (L^-1)_ki^2.
+ * stats: [batch][level][6] float64 = wmc, target, ci_lo, ci_hi, nobs, n_eff: wmc = sqrt(max_i
+ *   R^2_i) (a maximum below 0 by rounding counts as 0), target the first maximising i, ci =
+ *   tanh(atanh(wmc) -+ z / sqrt(n_eff - 3)), nobs = M_j.  r2 and stats are NULL together or not at all.
+ * Data-dependent rows (not errors): M_j <= 0: nobs = 0, everything else NaN; a series with
+ *   variance exactly 0: its corr row and column and the level's r2, wmc, target and ci NaN;
+ *   nobs < M, or a Cholesky pivot that is not > 0: r2, wmc, target and ci NaN; n_eff <= 3: ci NaN.
+ *   A matrix that is singular only up to rounding may give either NaN or values near 1.
+ * -1: a NULL bank, x or cov, ld < n, n_series < 2, level outside 1..62, boundary not 0 / 1, r2
+ *   without stats or stats without r2.
+ * -2: n_series > 16, n_series * n > 32768, n_taps > 40 (compose wtmi_modwt, Gram products and a
+ *   factorisation of its rows).  One workgroup per group: M smooth rows in LDS (128 KiB at
+ *   M n = 32768, one workgroup per CU): n <= 2048 at M = 16, 8192 at M = 4, 16384 at M = 2.   */
+int wtmi_modwt_wcmat(const float* x, long long ld, long long batch, int n_series, long long n,
+                     const double* dec_lo, const double* dec_hi, int n_taps, int level,
+                     int boundary, double z, double* cov, double* corr, double* r2,
+                     double* stats, void* stream);
+
 /* ---- per-series moments / affine (K9) -----------------------------------------
  * Replace standardize_series (src/utils/wavelet_helpers.py:22-57) and the
  * covariances of pycwt.ar1 (src/cwt.py:106).  out: [batch][8] float64 =

@@ -180,6 +180,15 @@ def wavelet_correlation_series(input_series, output_series, levels: int, filters
     return transforms.wavelet_correlation(input_series, output_series, levels, filters, max_lag=max_lag)
 
 
+def wavelet_correlation_matrix_series(series_list, levels: int, filters=MOTHER):
+    """How M series co-move at each MODWT scale (engine extension; the by-scale form of the
+    correlation table for all series at once): the wavelet covariance and correlation matrices of
+    the brick-wall coefficients and the wavelet multiple correlation with its 95 % interval, from
+    the series themselves in one fused launch (``wtmi_modwt_wcmat``): a
+    ``WaveletCorrelationMatrix`` ([B, M, N] input: a list), levels D_1 .. D_J."""
+    return transforms.wavelet_correlation_matrix(series_list, levels, filters)
+
+
 def plot_smoothing(smooth_signals: dict, original_t: npt.NDArray, original_y: npt.NDArray,
                    ascending: bool = False, **kwargs):
     """One panel per smoothed signal over the original (src/modwt.py:254-283)."""

@@ -1027,6 +1027,104 @@ def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torc
     return {"stats": stats, "xcorr": xcorr}
 
 
+# ------------------------- MODWT wavelet correlation matrix / multiple correlation
+WCMAT_MAX_SERIES = 16       # series per group of the fused kernel (include/wtmi.h: wtmi_modwt_wcmat)
+WCMAT_MAX_SAMPLES = 32768   # series x samples of a group: its smooth rows fill the workgroup's LDS
+WCMAT_STATS = ("wmc", "target", "ci_lo", "ci_hi", "nobs", "n_eff")
+
+
+def _wcmat_composed(x, lo, hi, level, periodic, z):
+    """The numbers of wtmi_modwt_wcmat from modwt coefficient rows, fp64 torch Gram products and
+    torch.linalg: (cov, corr [B, level, M, M], r2 [B, level, M], stats [B, level, 6])."""
+    B, M, n = x.shape
+    L = lo.size
+    nan = float("nan")
+    dev = x.device
+    rows = modwt((x - x[..., :1]).reshape(B * M, n), lo, hi, level)[:, :level].to(torch.float64)
+    rows = rows.reshape(B, M, level, n)
+    cov = torch.full((B, level, M, M), nan, dtype=torch.float64, device=dev)
+    corr, r2 = cov.clone(), cov[..., 0].clone()
+    stats = torch.full((B, level, 6), nan, dtype=torch.float64, device=dev)
+    eye = torch.eye(M, dtype=torch.float64, device=dev)
+    for j in range(1, level + 1):
+        t0 = 0 if periodic else min(n, ((1 << j) - 1) * (L - 1))
+        Mj = n - t0
+        stats[:, j - 1, 4] = max(Mj, 0)
+        if Mj <= 0:
+            continue
+        w = rows[:, :, j - 1, t0:]
+        c = w @ w.transpose(-1, -2) / Mj
+        c = torch.triu(c) + torch.triu(c, 1).transpose(-1, -2)  # symmetric bit for bit
+        var = torch.diagonal(c, dim1=-2, dim2=-1)
+        p = c / torch.sqrt(var.unsqueeze(-1) * var.unsqueeze(-2))
+        p = torch.where(eye.bool(), torch.where(var > 0, 1.0, nan).unsqueeze(-1).expand_as(p), p)
+        cov[:, j - 1], corr[:, j - 1] = c, p
+        neff = (n >> j) - (0 if periodic else (L - 2) - ((L - 2) >> j))
+        stats[:, j - 1, 5] = neff
+        ok = (var > 0).all(-1)
+        if Mj < M or not bool(ok.any()):
+            continue
+        fac, info = torch.linalg.cholesky_ex(torch.where(ok[:, None, None], p, eye))
+        ok = ok & (info == 0)
+        inv = torch.linalg.solve_triangular(torch.where(ok[:, None, None], fac, eye), eye.expand(B, M, M), upper=False)
+        r = torch.where(ok[:, None], 1.0 - 1.0 / (inv ** 2).sum(-2), nan)
+        r2[:, j - 1] = r
+        best, tgt = torch.nan_to_num(r, nan=-1.0).max(-1)
+        wmc = torch.where(ok, torch.sqrt(best.clamp_min(0.0)), nan)
+        stats[:, j - 1, 0], stats[:, j - 1, 1] = wmc, torch.where(ok, tgt.to(torch.float64), nan)
+        if neff > 3:
+            zr, hw = torch.atanh(wmc), z / float(neff - 3) ** 0.5
+            stats[:, j - 1, 2], stats[:, j - 1, 3] = torch.tanh(zr - hw), torch.tanh(zr + hw)
+    return cov, corr, r2, stats
+
+
+def modwt_wcmat(x: torch.Tensor, dec_lo, dec_hi, level: int, *, boundary: str = "brickwall",
+                ci_level: float = 0.95, want_corr: bool = True, want_multiple: bool = True):
+    """Wavelet covariance / correlation matrices and the wavelet multiple correlation
+    (Fernandez-Macho 2012) per MODWT detail level of groups of M float32 series x [B, M, n] (or
+    [M, n]): {"cov", "corr": [B, level, M, M] float64, "r2": [B, level, M] (R^2 of series i on the
+    others, 1 - 1 / (P^-1)_ii), "stats": [B, level, 6] (``WCMAT_STATS``: wmc = sqrt(max_i R^2_i),
+    target = the maximising series, the Fisher interval of wmc, nobs, n_eff)}; row j - 1 = level
+    j; entries not requested are None.  boundary and ci_level as ``modwt_wcorr``.  NaN rows: a
+    level without coefficients (nobs 0); a series without variance (its corr row and column, the
+    level's r2 / wmc / target / ci); fewer coefficients than series or a correlation matrix that
+    is not positive definite (r2 / wmc / target / ci); n_eff <= 3 (ci).  Groups of at most
+    ``WCMAT_MAX_SERIES`` series, ``WCMAT_MAX_SAMPLES`` series x samples and ``MRA_MAX_TAPS`` taps
+    take ONE fused launch (wtmi_modwt_wcmat); beyond, modwt rows, fp64 torch Gram products and
+    torch.linalg compose the same numbers."""
+    from statistics import NormalDist
+    what = "modwt_wcmat"
+    level = _int_level(level, 1, MRA_MAX_LEVEL, what)
+    lo, hi = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi)
+    if boundary not in WCORR_BOUNDARY:
+        raise ValueError(f"{what}: boundary must be one of {sorted(WCORR_BOUNDARY)}, got {boundary!r}")
+    if not 0.0 < ci_level < 1.0:
+        raise ValueError(f"{what}: ci_level must lie in (0, 1), got {ci_level!r}")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (2, 3) \
+            or x.shape[-2] < 2 or x.shape[-1] < 1:
+        raise ValueError(f"{what}: x must be float32 [series >= 2, n] or [batch, series >= 2, n] rows")
+    z = NormalDist().inv_cdf(0.5 + 0.5 * ci_level)
+    dev = _check_dev(x)
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    B, M, n = x.shape
+    if x.stride(2) != 1 or x.stride(1) < n or (B > 1 and x.stride(0) != M * x.stride(1)):
+        x = x.contiguous()  # the C ABI's layout: [batch][series][ld]
+    if M > WCMAT_MAX_SERIES or M * n > WCMAT_MAX_SAMPLES or lo.size > MRA_MAX_TAPS:
+        cov, corr, r2, stats = _wcmat_composed(x, lo, hi, level, boundary == "periodic", z)
+    else:
+        cov = torch.empty((B, level, M, M), dtype=torch.float64, device=dev)
+        corr = torch.empty_like(cov) if want_corr else None
+        r2 = torch.empty((B, level, M), dtype=torch.float64, device=dev) if want_multiple else None
+        stats = torch.empty((B, level, 6), dtype=torch.float64, device=dev) if want_multiple else None
+        with torch.cuda.device(dev):
+            _lib.call("wtmi_modwt_wcmat", _ptr(x), x.stride(1), B, M, n, _tp(lo), _tp(hi), lo.size, level,
+                      WCORR_BOUNDARY[boundary], C.c_double(z), _ptr(cov), _ptr(corr), _ptr(r2),
+                      _ptr(stats), _stream(dev))
+    return {"cov": cov, "corr": corr if want_corr else None, "r2": r2 if want_multiple else None,
+            "stats": stats if want_multiple else None}
+
+
 # ------------------------------------------------------------ torch custom ops
 # torch.ops.wtmi.* wrappers over the same HIP kernels (CUDA/ROCm dispatch only: a
 # CPU tensor has no kernel and raises).  Filter taps travel as host float64 tensors.
@@ -1214,6 +1312,21 @@ def _register():
     @_modwt_wcorr.register_fake
     def _(x, y, dec_lo, dec_hi, level, periodic):
         return x.new_empty((_batch(x), level, 8), dtype=torch.float64)
+
+    @lib.custom_op("wtmi::modwt_wcmat", mutates_args=())
+    def _modwt_wcmat(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, level: int, periodic: bool
+                     ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Wavelet covariance and correlation matrices [B, level, M, M], R^2 [B, level, M] and the
+        multiple-correlation rows (``WCMAT_STATS``) [B, level, 6] of groups x [B, M, n]."""
+        r = modwt_wcmat(x, dec_lo.cpu().numpy(), dec_hi.cpu().numpy(), level,
+                        boundary="periodic" if periodic else "brickwall")
+        return r["cov"], r["corr"], r["r2"], r["stats"]
+
+    @_modwt_wcmat.register_fake
+    def _(x, dec_lo, dec_hi, level, periodic):
+        B, M = _batch(x, 3), x.shape[-2]
+        return (x.new_empty((B, level, M, M), dtype=torch.float64), x.new_empty((B, level, M, M), dtype=torch.float64),
+                x.new_empty((B, level, M), dtype=torch.float64), x.new_empty((B, level, 6), dtype=torch.float64))
 
     @lib.custom_op("wtmi::series_stats", mutates_args=())
     def _series_stats(x: torch.Tensor) -> torch.Tensor:

@@ -904,3 +904,42 @@ def wavelet_variance(x, levels: int, wavelet, boundary: str = "brickwall"):
     """The wavelet variance of x per MODWT scale (``WaveletCorrelation.variance_x`` and nobs; the
     pair columns are NaN): [n] in gives one result, [B, n] in a list of B."""
     return wavelet_correlation(x, None, levels, wavelet, boundary=boundary)
+
+
+@dataclass
+class WaveletCorrelationMatrix:
+    """Wavelet covariance and correlation matrices of M series per MODWT detail level and their
+    wavelet multiple correlation (``ops.modwt_wcmat``).  Entry j - 1 of every array is level
+    ``names[j - 1]`` = D_j, scale 2^(j-1): covariance and correlation are [levels, M, M],
+    r_squared [levels, M] (series i regressed on the others), multiple_correlation [levels] =
+    sqrt(max_i r_squared), target [levels] the maximising series (-1 where undefined), ci
+    [levels, 2] the interval of multiple_correlation, nobs [levels]."""
+
+    names: List[str]
+    covariance: np.ndarray
+    correlation: np.ndarray
+    r_squared: np.ndarray
+    multiple_correlation: np.ndarray
+    target: np.ndarray
+    ci: np.ndarray
+    nobs: np.ndarray
+
+    @classmethod
+    def from_rows(cls, cov, corr, r2, stats) -> "WaveletCorrelationMatrix":
+        s = np.asarray(stats, dtype=np.float64)
+        if s.ndim != 2 or s.shape[1] != 6:
+            raise ValueError(f"stats must be [levels, 6], got {s.shape}")
+        tgt = np.where(np.isnan(s[:, 1]), -1, s[:, 1]).astype(np.int64)
+        return cls([f"D_{j}" for j in range(1, s.shape[0] + 1)], np.asarray(cov), np.asarray(corr), np.asarray(r2),
+                   s[:, 0].copy(), tgt, s[:, 2:4].copy(), s[:, 4].astype(np.int64))
+
+
+def wavelet_correlation_matrix(series, levels: int, wavelet, boundary: str = "brickwall", ci_level: float = 0.95):
+    """The wavelet correlation matrix of M series at every MODWT scale and their wavelet multiple
+    correlation, one fused launch for a whole batch: [M, n] series (or a list of M equally long
+    ones) give one ``WaveletCorrelationMatrix``, [B, M, n] a list of B."""
+    w = as_filter_bank(wavelet)
+    xd = _to_dev(series if isinstance(series, torch.Tensor) else np.asarray(series), torch.float32)
+    res = ops.modwt_wcmat(xd, w.dec_lo, w.dec_hi, int(levels), boundary=boundary, ci_level=ci_level)
+    out = [WaveletCorrelationMatrix.from_rows(*r) for r in zip(*(_np(res[k]) for k in ("cov", "corr", "r2", "stats")))]
+    return out[0] if xd.dim() == 2 else out
