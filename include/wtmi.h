@@ -375,6 +375,44 @@ int wtmi_modwt_wcmat(const float* x, long long ld, long long batch, int n_series
                      int boundary, double z, double* cov, double* corr, double* r2,
                      double* stats, void* stream);
 
+/* ---- MODWT translation-invariant wavelet shrinkage with MAD thresholds (K26) -----------
+ * The undecimated counterpart of wtmi_dwt_denoise (Coifman & Donoho's cycle spinning; Percival &
+ * Walden 2000, ch. 10.5-10.6): wtmi_modwt of every series, a threshold per detail level, the
+ * shrink of wtmi_dwt_denoise applied to every W~_j, and wtmi_imodwt of the shrunk rows, in one
+ * launch.  V~_J is never modified.  The result does not depend on where the series starts.
+ * x: [batch][ld] float32; dec_*: HOST pointers to the n_taps filters.  The passes run on
+ * x - x[0]; x[0] returns at the end (a constant series comes back exactly).
+ * rule 0 (fixed): lambda_j = thresholds[b * thr_ld + j - 1], DEVICE float64; thr_ld = 0: one
+ *   [level] row for every series, else thr_ld >= level.  mult is ignored, sigma_j is NaN.
+ * rule 1 (universal): sigma = sqrt2 median(|W~_1|) / 0.6744897501960817 (the series' own units)
+ *   and lambda_j = mult sigma sqrt(2 ln n) / 2^(j/2).
+ * rule 2 (level-dependent): sigma_j = 2^(j/2) median(|W~_j|) / 0.6744897501960817 and lambda_j =
+ *   mult sigma_j sqrt(2 ln n) / 2^(j/2).  The median, sigma, lambda, the fp32 comparison against
+ *   (float)lambda_j and shrink 0 / 1 / 2 (soft, hard, garrote) are those of wtmi_dwt_denoise.
+ * out: [batch][ld_out] float32.  lambda = 0 returns x.
+ * info: NULL, or [batch][level][4] float64, row j-1 = sigma_j, lambda_j, kept_j, n.
+ * coeffs: NULL, or [batch][level+1][n] float32, the shrunk rows in wtmi_modwt's row order
+ *   [W~_1 .. W~_J, V~_J].
+ * workspace: DEVICE, wtmi_modwt_denoise_workspace_bytes(batch, n, level) bytes; may be NULL when
+ *   that is 0 or when coeffs is given (the spilled rows then live in coeffs).  No allocation
+ *   inside the call.  One workgroup per series keeps, in floats with np = n rounded up to 4, the
+ *   V row [0, np) and the R = min(level, 36864 / np - 1) COARSEST coefficient rows in LDS, W~_j
+ *   at [np (j - S), np (j - S + 1)); the S = level - R finest rows go to the workspace, series b's
+ *   W~_j at float offset (b S + j - 1) n: batch * S * n * 4 bytes (0 for n = 1333, level 7;
+ *   9 * 16384 * 4 per series for n = 16384, level 10).  -1 from the size query: bad geometry.
+ * -1: a NULL bank pointer or NULL out, ld < n, ld_out < n, level outside 1..62, rule or shrink
+ *   outside 0..2, mult < 0 or not finite, rule 0 without thresholds or with 0 < thr_ld < level,
+ *   spilled rows with neither workspace nor coeffs.
+ * -2: n > 16384 or n_taps > 40 (compose wtmi_modwt, a shrink of its rows and wtmi_imodwt).  A
+ *   series shorter than the dilated filter is exact (the offsets wrap).  Non-finite input
+ *   samples are unspecified.                                                                  */
+long long wtmi_modwt_denoise_workspace_bytes(long long batch, long long n, int level);
+int wtmi_modwt_denoise(const float* x, long long ld, long long batch, long long n,
+                       const double* dec_lo, const double* dec_hi, int n_taps, int level, int rule,
+                       int shrink, double mult, const double* thresholds, long long thr_ld,
+                       float* out, long long ld_out, double* info, float* coeffs, void* workspace,
+                       void* stream);
+
 /* ---- per-series moments / affine (K9) -----------------------------------------
  * Replace standardize_series (src/utils/wavelet_helpers.py:22-57) and the
  * covariances of pycwt.ar1 (src/cwt.py:106).  out: [batch][8] float64 =

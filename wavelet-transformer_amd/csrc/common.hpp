@@ -198,6 +198,9 @@ struct Options {
                             // boxcar: K itself (1, K <= 12; r05) or the largest of 6..1 dividing
                             // K (0, r04).  C4 serial trace: phase B 0.2935 -> 0.2840 ms, boxcar
                             // 0.2538 -> 0.2515; 64-pair step 0.4499 -> 0.4434 (alternating)
+  int modwt_den_stage = 1;  // WTMI_MODWT_DEN_STAGE: K26's synthesis copies a spilled coefficient row
+                            // into a freed LDS row slot before its tap loop (1), or the tap loop
+                            // gathers it from memory (0); profiles/r14/INDEX.md
 };
 const Options& options();
 

@@ -189,6 +189,25 @@ def wavelet_correlation_matrix_series(series_list, levels: int, filters=MOTHER):
     return transforms.wavelet_correlation_matrix(series_list, levels, filters)
 
 
+def denoise_signal_series(series_list, levels: int, filters=MOTHER, rule: str = "universal", shrink: str = "soft",
+                          mult: float = 1.0):
+    """Translation-invariant wavelet shrinkage of many series (engine extension; the MODWT
+    counterpart of ``src.dwt.denoise_signal_batch``): per entry {"signal": the denoised series,
+    "sigma", "threshold", "kept": one value per detail level 1 .. levels}.  rule "universal" or
+    "level", shrink "soft", "hard" or "garrote", as ``wtmi.transforms.modwt_denoise``.  Series of
+    one length share ONE fused launch (``wtmi_modwt_denoise``)."""
+    out: list = [None] * len(series_list)
+    groups: dict = {}
+    for i, s in enumerate(series_list):
+        groups.setdefault(len(s), []).append(i)
+    for idx in groups.values():
+        rows = np.stack([np.asarray(series_list[i], dtype=np.float64) for i in idx])
+        sig, info = transforms.modwt_denoise(rows, filters, levels, rule, shrink, mult, return_info=True)
+        for k, s, t in zip(idx, sig, info):
+            out[k] = {"signal": s, "sigma": t[:, 0], "threshold": t[:, 1], "kept": t[:, 2].astype(np.int64)}
+    return out
+
+
 def plot_smoothing(smooth_signals: dict, original_t: npt.NDArray, original_y: npt.NDArray,
                    ascending: bool = False, **kwargs):
     """One panel per smoothed signal over the original (src/modwt.py:254-283)."""

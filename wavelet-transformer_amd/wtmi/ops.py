@@ -934,6 +934,96 @@ def modwt_mra_rows(w: torch.Tensor, dec_lo, dec_hi) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------ MODWT translation-invariant shrinkage
+MODWT_DENOISE_MAX_N = 16384  # longest row of the fused kernel (include/wtmi.h: wtmi_modwt_denoise)
+
+
+def _modwt_denoise_composed(x, lo, hi, level, rule, shrink, mult, thr):
+    """The numbers of wtmi_modwt_denoise from modwt rows, torch order statistics and ``where`` per
+    level, and imodwt: (denoised [B, n], info [B, level, 4], shrunk rows [B, level + 1, n])."""
+    B, n = x.shape
+    w = modwt(x, lo, hi, level)
+    info = torch.full((B, level, 4), float("nan"), dtype=torch.float64, device=x.device)
+    scale = mult * float(np.sqrt(2.0 * np.log(n)))
+    base = None
+    for j in range(1, level + 1):
+        c = w[:, j - 1]
+        mag = c.abs()
+        up = 2.0 ** (j // 2) * (float(np.sqrt(2.0)) if j & 1 else 1.0)  # 2^(j/2)
+        if rule == 0:
+            lam = thr[:, j - 1]
+        else:
+            if rule == 2 or j == 1:
+                s = torch.sort(mag, dim=1).values[:, [(n - 1) // 2, n // 2]].to(torch.float64)
+                s0 = 0.5 * (s[:, 0] + s[:, 1]) / MAD_SCALE
+                base = float(np.sqrt(2.0)) * s0  # universal: sigma
+            lam = scale * s0 if rule == 2 else scale * base / up
+            info[:, j - 1, 0] = s0 * up if rule == 2 else base
+        lf = lam.to(torch.float32)[:, None]
+        keep = mag >= lf if shrink == 1 else mag > lf
+        if shrink == 0:
+            val = torch.copysign(mag - lf, c)
+        elif shrink == 1:
+            val = c
+        else:
+            val = c - lf * (lf / torch.where(keep, c, torch.ones_like(c)))
+        c.copy_(torch.where(keep, val, torch.zeros_like(c)))
+        info[:, j - 1, 1] = lam
+        info[:, j - 1, 2] = keep.sum(dim=1)
+        info[:, j - 1, 3] = n
+    return imodwt(w, lo, hi), info, w
+
+
+def modwt_denoise(x: torch.Tensor, dec_lo, dec_hi, level: int, *, rule: str = "universal",
+                  shrink: str = "soft", mult: float = 1.0, thresholds=None, want_info: bool = True,
+                  want_coeffs: bool = False):
+    """Translation-invariant wavelet shrinkage of float32 rows x ([n] or [B, n]): modwt, a threshold
+    per detail level, the shrink of ``dwt_denoise`` on every W~_j, and imodwt of the shrunk rows:
+    {"denoised": [B, n] float32, "info": [B, level, 4] float64 (``DENOISE_INFO``, row j - 1 =
+    level j) or None, "coeffs": [B, level + 1, n] float32 (the shrunk rows, modwt's row order) or
+    None}.  rule "universal": lambda_j = mult sigma sqrt(2 ln n) / 2^(j/2) with sigma = sqrt2
+    median(|W~_1|) / ``MAD_SCALE``; "level": the same with sigma_j = 2^(j/2) median(|W~_j|) /
+    ``MAD_SCALE``; "fixed": ``thresholds`` ([level] or [B, level], float64) and mult ignored.
+    shrink: "soft", "hard" or "garrote".  Rows of at most ``MODWT_DENOISE_MAX_N`` samples and
+    filters of at most ``MRA_MAX_TAPS`` taps take ONE fused launch (wtmi_modwt_denoise); beyond,
+    modwt, torch order statistics and imodwt compose the same numbers."""
+    what = "modwt_denoise"
+    level = _int_level(level, 1, MRA_MAX_LEVEL, what)
+    lo, hi = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi)
+    if rule not in DENOISE_RULES:
+        raise ValueError(f"{what}: rule must be one of {sorted(DENOISE_RULES)}, got {rule!r}")
+    if shrink not in DENOISE_SHRINK:
+        raise ValueError(f"{what}: shrink must be one of {sorted(DENOISE_SHRINK)}, got {shrink!r}")
+    mult = float(mult)
+    if not (mult >= 0.0 and np.isfinite(mult)):
+        raise ValueError(f"{what}: mult must be finite and >= 0, got {mult!r}")
+    fixed = rule == "fixed"
+    if fixed != (thresholds is not None):
+        raise ValueError(f"{what}: thresholds go with rule 'fixed' and with no other")
+    if fixed and (len(_shape(thresholds)) not in (1, 2) or _shape(thresholds)[-1] != level):
+        raise ValueError(f"{what}: thresholds must be [{level}] or [batch, {level}], got shape "
+                         f"{_shape(thresholds)}")
+    dev, x, _ = _series_or_pair(x, None, what, True)
+    B, n = x.shape
+    thr = _f64_dev(thresholds, dev)
+    if fixed and thr.dim() == 2 and thr.shape[0] != B:
+        raise ValueError(f"{what}: {thr.shape[0]} threshold rows for {B} series")
+    r, s = DENOISE_RULES[rule], DENOISE_SHRINK[shrink]
+    if n > MODWT_DENOISE_MAX_N or lo.size > MRA_MAX_TAPS:
+        den, info, coeffs = _modwt_denoise_composed(x, lo, hi, level, r, s, mult,
+                                                    thr.reshape(-1, level).expand(B, level) if fixed else None)
+        return {"denoised": den, "info": info if want_info else None, "coeffs": coeffs if want_coeffs else None}
+    den = torch.empty((B, n), dtype=torch.float32, device=dev)
+    info = torch.empty((B, level, 4), dtype=torch.float64, device=dev) if want_info else None
+    coeffs = torch.empty((B, level + 1, n), dtype=torch.float32, device=dev) if want_coeffs else None
+    ws = None if want_coeffs else _scratch(_lib.call("wtmi_modwt_denoise_workspace_bytes", B, n, level), dev)
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_modwt_denoise", _ptr(x), x.stride(0), B, n, _tp(lo), _tp(hi), lo.size, level, r, s,
+                  C.c_double(mult), _ptr(thr), level if fixed and thr.dim() == 2 else 0,
+                  _ptr(den), n, _ptr(info), _ptr(coeffs), _ptr(ws), _stream(dev))
+    return {"denoised": den, "info": info, "coeffs": coeffs}
+
+
 # ------------------------------------------- MODWT wavelet variance / correlation
 WCORR_MAX_N = 16384      # longest row of the fused kernel (include/wtmi.h: wtmi_modwt_wcorr)
 WCORR_MAX_LAG_N = 8192   # with max_lag > 0: the coefficient rows share the workgroup's LDS

@@ -823,6 +823,24 @@ def modwt_mra(x, wavelet, level, smooths=False):
     return tuple(out) if smooths else out[0]
 
 
+def modwt_denoise(data, wavelet, level, rule="universal", shrink="soft", mult=1.0, thresholds=None,
+                  return_info=False):
+    """Translation-invariant wavelet shrinkage (thresholded MODWT rows, inverted) of an [n] series
+    (or a [B, n] batch) in one fused launch: fp64 samples of the same shape.  rule / shrink / mult /
+    thresholds as ``ops.modwt_denoise``.  return_info: also the fp64 [level, 4] table
+    (``[B, level, 4]`` for a batch) of sigma, threshold, kept and length per detail level."""
+    w = as_filter_bank(wavelet)
+    a = np.asarray(data)
+    res = ops.modwt_denoise(_to_dev(a, torch.float32), w.dec_lo, w.dec_hi, int(level), rule=rule, shrink=shrink,
+                            mult=mult, thresholds=thresholds, want_info=return_info)
+    out = _np(res["denoised"], np.float64)
+    out = out[0] if a.ndim == 1 else out
+    if not return_info:
+        return out
+    info = _np(res["info"], np.float64)
+    return out, (info[0] if a.ndim == 1 else info)
+
+
 def modwt_mra_rows(wc, wavelet):
     """The reference's modwtmra(w, filters) of existing rows [W_1 .. W_J, V_J] ([J + 1, n] or
     [B, J + 1, n]), one launch."""
