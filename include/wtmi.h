@@ -344,6 +344,41 @@ int wtmi_modwt_wcorr(const float* x, const float* y, long long ld, long long bat
                      const double* dec_lo, const double* dec_hi, int n_taps, int level,
                      int boundary, int max_lag, double z, double* stats, double* xcorr, void* stream);
 
+/* ---- Time-localized (rolling-window) MODWT wavelet correlation (K27) --------------------
+ * When the co-movement of wtmi_modwt_wcorr's table changed: the rolling-window wavelet correlation
+ * (Ranta 2010; Gencay, Selcuk & Whitcher ch. 7 in rolling form) and its weighted generalisation,
+ * the local wavelet correlation of Fernandez-Macho (2018; wlmc of the R package wavemulcor) for
+ * one pair: a symmetric window theta(k), |k| <= H = half_width, slid over the coefficients W_j of
+ * wtmi_modwt (detail levels 1..level), which are formed in LDS and never written out.
+ * x / y: [batch][ld] float32; y NULL for a single series (the local wavelet variance only).  The
+ *   passes run on x - x[0], y - y[0].  dec_*: HOST pointers to the n_taps filters.
+ * window: DEVICE float64 [half_width + 1], window[k] = theta(k) >= 0, theta(0) > 0 (other values:
+ *   unspecified results).
+ * For every centre s in [0, n) the counted coefficients C(s) are
+ *   boundary 1 (brick wall): t in [max(t0, s - H), min(n - 1, s + H)], t0 = (2^j - 1)(n_taps - 1) as
+ *     wtmi_modwt_wcorr: the window is cut at the wall and at the series end and never wraps;
+ *   boundary 0 (periodic): t = (s + k) mod n for every |k| <= H (2 H + 1 <= n: none counts twice).
+ * In fp64 from the fp32 coefficients: Sw(s) = sum_C(s) theta(t - s) and A^ab(s) = sum_C(s)
+ *   theta(t - s) W^a_j[t] W^b_j[t], ab in {xx, yy, xy}.
+ * corr: NULL, or [batch][level][ld_out] float32, row j-1: A^xy / sqrt(A^xx A^yy) clamped to [-1, 1].
+ * moments: NULL, or [batch][level][3][ld_out] float32, planes A^xx / Sw, A^yy / Sw, A^xy / Sw (the
+ *   local wavelet variances and covariance).  Without y only plane 0 is written; planes 1 and 2
+ *   are left untouched.  Both are computed in fp64 and rounded once.
+ * Data-dependent values (not errors): Sw(s) = 0 (no counted coefficient in the window): all four
+ *   NaN; A^xx = 0 or A^yy = 0 (a window without energy): corr NaN, that variance and the
+ *   covariance 0.
+ * -1: a NULL bank or window, ld < n, ld_out < n, level outside 1..62, boundary not 0 / 1,
+ *   half_width < 0, periodic with 2 half_width + 1 > n, corr and moments both NULL, corr without y.
+ * -2: n > 8192, n_taps > 40, half_width > 1024 (compose wtmi_modwt and windowed reductions over
+ *   its rows).  One workgroup per pair: two smooth rows, two coefficient rows with a halo of
+ *   half_width on either side and the weights in LDS (152 KiB at n = 8192, half_width = 1024, one
+ *   workgroup per CU).  A series shorter than the dilated filter is exact (the offsets wrap).
+ *   Equal inputs give equal bits (no atomics).                                                */
+int wtmi_modwt_lwcorr(const float* x, const float* y, long long ld, long long batch, long long n,
+                      const double* dec_lo, const double* dec_hi, int n_taps, int level,
+                      int boundary, const double* window, int half_width,
+                      float* corr, float* moments, long long ld_out, void* stream);
+
 /* ---- MODWT wavelet correlation matrix / wavelet multiple correlation (K25) -------------
  * K22 for M series at once: the wavelet covariance and correlation matrices of all M series of a
  * group at every MODWT detail level (the by-scale correlation_matrix_pvalues table itself) and

@@ -180,6 +180,18 @@ def wavelet_correlation_series(input_series, output_series, levels: int, filters
     return transforms.wavelet_correlation(input_series, output_series, levels, filters, max_lag=max_lag)
 
 
+def local_wavelet_correlation_series(input_series, output_series, levels: int, half_width: int, filters=MOTHER,
+                                     window="uniform"):
+    """When the co-movement of two series at each MODWT scale changed (engine extension; the
+    rolling form of ``wavelet_correlation_series``): the wavelet correlation, variances and
+    covariance of the brick-wall coefficients under a window of 2 half_width + 1 samples ("uniform",
+    "bartlett", "gaussian" or explicit weights) centred at every sample, with the 95 % interval,
+    from the series themselves in one fused launch (``wtmi_modwt_lwcorr``): a
+    ``LocalWaveletCorrelation`` ([B, N] inputs: a list), levels D_1 .. D_J."""
+    return transforms.local_wavelet_correlation(input_series, output_series, levels, filters, half_width,
+                                                window=window)
+
+
 def wavelet_correlation_matrix_series(series_list, levels: int, filters=MOTHER):
     """How M series co-move at each MODWT scale (engine extension; the by-scale form of the
     correlation table for all series at once): the wavelet covariance and correlation matrices of

@@ -60,6 +60,7 @@ PROTOTYPES = {
     "wtmi_modwt_mra": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "wtmi_modwt_mra_rows": (_I32, [_P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
     "wtmi_modwt_wcorr": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _F64, _P, _P, _P]),
+    "wtmi_modwt_lwcorr": (_I32, [_P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _I64, _P]),
     "wtmi_modwt_wcmat": (_I32, [_P, _I64, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P]),
     "wtmi_modwt_denoise_workspace_bytes": (_I64, [_I64, _I64, _I32]),
     "wtmi_modwt_denoise": (_I32, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _F64, _P, _I64,

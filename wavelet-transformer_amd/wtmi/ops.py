@@ -1117,8 +1117,114 @@ def modwt_wcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torc
     return {"stats": stats, "xcorr": xcorr}
 
 
+# ------------------------- MODWT time-localized (rolling-window) wavelet correlation
+LWCORR_MAX_N = 8192           # longest row of the fused kernel (include/wtmi.h: wtmi_modwt_lwcorr)
+LWCORR_MAX_HALF_WIDTH = 1024  # widest window: the rows' halos and the weights share the workgroup's LDS
+LWCORR_MOMENTS = ("var_x", "var_y", "cov")
+_LWCORR_BLOCK = 1024          # centres per Toeplitz product of the composed route
+
+
+def _lwcorr_composed(x, y, lo, hi, level, theta, periodic):
+    """The numbers of wtmi_modwt_lwcorr from modwt coefficient rows and fp64 torch windowed sums
+    (products of the padded rows with one banded Toeplitz block of the weights): (corr
+    [B, level, n] or None without y, moments [B, level, 3, n]) float32; without y planes 1 and 2
+    of moments are NaN."""
+    B, n = x.shape
+    L, H, dev, nan = lo.size, theta.size - 1, x.device, float("nan")
+    th = torch.as_tensor(theta, dtype=torch.float64, device=dev)
+    cb = min(n, _LWCORR_BLOCK)
+    k = (torch.arange(cb + 2 * H, device=dev)[:, None] - H - torch.arange(cb, device=dev)[None, :]).abs()
+    toep = torch.where(k <= H, th[k.clamp_max(H)], torch.zeros((), dtype=torch.float64, device=dev))
+
+    def windowed(q):  # [R, n] -> [R, n]: sum_k theta(k) q[s + k], zeros (or the wrap) outside
+        qp = torch.cat((q[:, n - H:], q, q[:, :H]), 1) if periodic else torch.nn.functional.pad(q, (H, H))
+        out = torch.empty_like(q)
+        for s in range(0, n, cb):
+            c = min(cb, n - s)
+            out[:, s:s + c] = qp[:, s:s + c + 2 * H] @ toep[:c + 2 * H, :c]
+        return out
+
+    rows = [modwt(r - r[:, :1], lo, hi, level)[:, :level].to(torch.float64) for r in ((x,) if y is None else (x, y))]
+    corr = None if y is None else torch.full((B, level, n), nan, dtype=torch.float32, device=dev)
+    mom = torch.full((B, level, 3, n), nan, dtype=torch.float32, device=dev)
+    for j in range(1, level + 1):
+        t0 = 0 if periodic else min(n, ((1 << j) - 1) * (L - 1))
+        counted = torch.ones((1, n), dtype=torch.float64, device=dev)
+        counted[:, :t0] = 0.0
+        sw = windowed(counted)
+        wx = rows[0][:, j - 1] * counted
+        axx = windowed(wx * wx)
+        mom[:, j - 1, 0] = torch.where(sw > 0, axx / sw, nan)
+        if y is None:
+            continue
+        wy = rows[1][:, j - 1] * counted
+        ayy, axy = windowed(wy * wy), windowed(wx * wy)
+        mom[:, j - 1, 1] = torch.where(sw > 0, ayy / sw, nan)
+        mom[:, j - 1, 2] = torch.where(sw > 0, axy / sw, nan)
+        ok = (sw > 0) & (axx > 0) & (ayy > 0)
+        corr[:, j - 1] = torch.where(ok, (axy / torch.sqrt(axx * ayy)).clamp(-1.0, 1.0), nan)
+    return corr, mom
+
+
+def _lwcorr_window(window, what):
+    """The weights theta(0 .. H) as contiguous float64 (host): 1-D, finite, >= 0, theta(0) > 0."""
+    if isinstance(window, torch.Tensor):
+        window = window.detach().cpu().numpy()
+    th = np.ascontiguousarray(np.asarray(window, dtype=np.float64))
+    if th.ndim != 1 or th.size < 1:
+        raise ValueError(f"{what}: window must hold the half_width + 1 weights theta(0 .. H), got shape {th.shape}")
+    if not np.isfinite(th).all() or (th < 0).any():
+        raise ValueError(f"{what}: window weights must be finite and >= 0")
+    if not th[0] > 0:
+        raise ValueError(f"{what}: the centre weight window[0] must be > 0, got {th[0]!r}")
+    return th
+
+
+def modwt_lwcorr(x: torch.Tensor, dec_lo, dec_hi, level: int, *, y: Optional[torch.Tensor] = None,
+                 window, boundary: str = "brickwall", moments: bool = False):
+    """Time-localized (rolling-window) wavelet variance, covariance and correlation per MODWT
+    detail level of float32 rows x ([n] or [B, n]) and, with y, of the pairs (x, y).  window: the
+    H + 1 weights theta(0 .. H) >= 0 of a symmetric window, theta(0) > 0.  For every centre s the
+    counted coefficients C(s) are t in [max(t0, s - H), min(n - 1, s + H)] (boundary "brickwall":
+    t0 = (2^j - 1)(taps - 1) as ``modwt_wcorr``; the window is cut, it never wraps) or (s + k) mod n
+    for |k| <= H ("periodic"; needs 2 H + 1 <= n).  With Sw = sum_C theta and A^ab = sum_C theta
+    W^a_j W^b_j in fp64: {"corr": [B, level, n] float32 = A^xy / sqrt(A^xx A^yy) clamped to
+    [-1, 1] (None without y), "moments": [B, level, 3, n] float32 (``LWCORR_MOMENTS``: A^xx / Sw,
+    A^yy / Sw, A^xy / Sw; None unless moments=True; without y planes 1 and 2 are NaN)}; row
+    j - 1 = level j.  NaN: Sw = 0 (no counted coefficient in the window: all four), A^xx = 0 or
+    A^yy = 0 (corr).  Rows of at most ``LWCORR_MAX_N`` samples, ``MRA_MAX_TAPS`` taps and windows
+    of half width at most ``LWCORR_MAX_HALF_WIDTH`` take ONE fused launch (wtmi_modwt_lwcorr);
+    beyond, modwt rows and fp64 torch windowed sums compose the same numbers."""
+    what = "modwt_lwcorr"
+    level = _int_level(level, 1, MRA_MAX_LEVEL, what)
+    lo, hi = _bank(what, dec_lo=dec_lo, dec_hi=dec_hi)
+    if boundary not in WCORR_BOUNDARY:
+        raise ValueError(f"{what}: boundary must be one of {sorted(WCORR_BOUNDARY)}, got {boundary!r}")
+    th = _lwcorr_window(window, what)
+    H = th.size - 1
+    # the window checks come before the operands': those end on the device
+    if boundary == "periodic" and isinstance(x, torch.Tensor) and x.dim() and 2 * H + 1 > x.shape[-1]:
+        raise ValueError(f"{what}: a periodic window of half width {H} needs 2 * {H} + 1 <= n = {x.shape[-1]} "
+                         "(no coefficient may count twice)")
+    dev, x, y = _series_or_pair(x, y, what, bool(moments))
+    B, n = x.shape
+    if n > LWCORR_MAX_N or lo.size > MRA_MAX_TAPS or H > LWCORR_MAX_HALF_WIDTH:
+        corr, mom = _lwcorr_composed(x, y, lo, hi, level, th, boundary == "periodic")
+        return {"corr": corr, "moments": mom if moments else None}
+    corr = None if y is None else torch.empty((B, level, n), dtype=torch.float32, device=dev)
+    mom = None
+    if moments:  # a single series fills plane 0 only
+        mom = torch.empty((B, level, 3, n), dtype=torch.float32, device=dev)
+        if y is None:
+            mom.fill_(float("nan"))
+    with torch.cuda.device(dev):
+        _lib.call("wtmi_modwt_lwcorr", _ptr(x), _ptr(y), x.stride(0), B, n, _tp(lo), _tp(hi), lo.size, level,
+                  WCORR_BOUNDARY[boundary], _ptr(_f64_dev(th, dev)), H, _ptr(corr), _ptr(mom), n, _stream(dev))
+    return {"corr": corr, "moments": mom}
+
+
 # ------------------------- MODWT wavelet correlation matrix / multiple correlation
-WCMAT_MAX_SERIES = 16       # series per group of the fused kernel (include/wtmi.h: wtmi_modwt_wcmat)
+WCMAT_MAX_SERIES = 16      # series per group of the fused kernel (include/wtmi.h: wtmi_modwt_wcmat)
 WCMAT_MAX_SAMPLES = 32768   # series x samples of a group: its smooth rows fill the workgroup's LDS
 WCMAT_STATS = ("wmc", "target", "ci_lo", "ci_hi", "nobs", "n_eff")
 
@@ -1402,6 +1508,20 @@ def _register():
     @_modwt_wcorr.register_fake
     def _(x, y, dec_lo, dec_hi, level, periodic):
         return x.new_empty((_batch(x), level, 8), dtype=torch.float64)
+
+    @lib.custom_op("wtmi::modwt_lwcorr", mutates_args=())
+    def _modwt_lwcorr(x: torch.Tensor, y: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor,
+                      window: torch.Tensor, level: int, periodic: bool) -> tuple[torch.Tensor, torch.Tensor]:
+        """Rolling-window wavelet correlation [B, level, n] and local variances / covariance
+        (``LWCORR_MOMENTS``) [B, level, 3, n] of row pairs; window: the weights theta(0 .. H)."""
+        r = modwt_lwcorr(x, dec_lo.cpu().numpy(), dec_hi.cpu().numpy(), level, y=y, window=window, moments=True,
+                         boundary="periodic" if periodic else "brickwall")
+        return r["corr"], r["moments"]
+
+    @_modwt_lwcorr.register_fake
+    def _(x, y, dec_lo, dec_hi, window, level, periodic):
+        B, n = _batch(x), x.shape[-1]
+        return (x.new_empty((B, level, n), dtype=torch.float32), x.new_empty((B, level, 3, n), dtype=torch.float32))
 
     @lib.custom_op("wtmi::modwt_wcmat", mutates_args=())
     def _modwt_wcmat(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, level: int, periodic: bool

@@ -924,6 +924,112 @@ def wavelet_variance(x, levels: int, wavelet, boundary: str = "brickwall"):
     return wavelet_correlation(x, None, levels, wavelet, boundary=boundary)
 
 
+LOCAL_WINDOWS = ("uniform", "bartlett", "gaussian")
+
+
+def local_window(window, half_width: int) -> np.ndarray:
+    """The weights theta(0 .. H) of a symmetric rolling window of half width H = half_width:
+    "uniform" theta = 1, "bartlett" theta(k) = 1 - k / (H + 1), "gaussian" theta(k) =
+    exp(-k^2 / (2 sigma^2)) with sigma = H / 3 (H = 0: the single weight 1), or an explicit array
+    of H + 1 non-negative weights with theta(0) > 0."""
+    if int(half_width) != half_width or half_width < 0:
+        raise ValueError(f"half_width must be an integer >= 0, got {half_width!r}")
+    H = int(half_width)
+    k = np.arange(H + 1, dtype=np.float64)
+    if isinstance(window, str):
+        if window not in LOCAL_WINDOWS:
+            raise ValueError(f"window must be one of {LOCAL_WINDOWS} or an array of weights, got {window!r}")
+        if window == "uniform":
+            return np.ones(H + 1)
+        if window == "bartlett":
+            return 1.0 - k / (H + 1)
+        return np.exp(-k * k / (2.0 * (H / 3.0) ** 2)) if H else np.ones(1)
+    th = ops._lwcorr_window(window, "local_window")
+    if th.size != H + 1:
+        raise ValueError(f"an explicit window must hold half_width + 1 = {H + 1} weights, got {th.size}")
+    return th
+
+
+def local_n_eff(theta, n: int, n_taps: int, levels: int, boundary: str = "brickwall") -> np.ndarray:
+    """[levels, n]: the effective number of independent coefficients under the window at centre s,
+    n_eff(j, s) = floor(K(s) / 2^j) with Kish's effective count K(s) = Sw(s)^2 / sum_C(s) theta^2 of
+    the counted coefficients C(s) of ``ops.modwt_lwcorr`` (0 where none counts).  For a uniform
+    periodic window over the whole series this is ``modwt_wcorr``'s floor(n / 2^j)."""
+    th = np.asarray(theta, dtype=np.float64)
+    H = th.size - 1
+    sym = np.concatenate((th[:0:-1], th))
+    out = np.zeros((levels, n))
+    for j in range(1, levels + 1):
+        if boundary == "periodic":
+            sw, s2 = np.full(n, sym.sum()), np.full(n, (sym * sym).sum())
+        else:
+            counted = (np.arange(n) >= min(n, (2 ** j - 1) * (n_taps - 1))).astype(np.float64)
+            sw, s2 = (np.convolve(counted, w)[H:H + n] for w in (sym, sym * sym))
+        with np.errstate(all="ignore"):
+            out[j - 1] = np.where(s2 > 0, np.floor(sw * sw / s2 / 2.0 ** j), 0.0)
+    return out
+
+
+@dataclass
+class LocalWaveletCorrelation:
+    """Time-localized wavelet variance, covariance and correlation of a pair of series per MODWT
+    detail level and time (``ops.modwt_lwcorr``).  Row j - 1 of every array is level
+    ``names[j - 1]`` = D_j, column s the window centred at sample s: variance_x, variance_y,
+    covariance, correlation and n_eff are [levels, n], ci is [levels, n, 2] (lower, upper).  NaN
+    where the window holds no counted coefficient (or no energy: correlation); ci also where
+    n_eff <= 3.  For a single series (``local_wavelet_variance``) only variance_x and n_eff are
+    numbers."""
+
+    names: List[str]
+    variance_x: np.ndarray
+    variance_y: np.ndarray
+    covariance: np.ndarray
+    correlation: np.ndarray
+    ci: np.ndarray
+    n_eff: np.ndarray
+    half_width: int
+
+
+def local_wavelet_correlation(x, y, levels: int, wavelet, half_width: int, window="uniform",
+                              boundary: str = "brickwall", ci_level: float = 0.95):
+    """When two series co-move at each MODWT scale: the rolling-window wavelet correlation (Ranta
+    2010) or, with a weighted window, the local wavelet correlation of Fernandez-Macho (2018),
+    with the local wavelet variances and covariance, one fused launch for a whole batch: [n]
+    inputs give one ``LocalWaveletCorrelation``, [B, n] inputs a list of B.  window: see
+    ``local_window``; boundary as ``ops.modwt_lwcorr``.  The interval is Fisher's, ci =
+    tanh(atanh(correlation) -+ z / sqrt(n_eff - 3)) with ``local_n_eff``.  That count is this
+    project's own definition for a cut (brick-wall) or weighted window; it reduces to
+    ``wavelet_correlation``'s floor(n / 2^j) for a uniform periodic window over the whole series."""
+    from statistics import NormalDist
+    if not 0.0 < ci_level < 1.0:
+        raise ValueError(f"ci_level must lie in (0, 1), got {ci_level!r}")
+    w = as_filter_bank(wavelet)
+    th = local_window(window, half_width)
+    levels = int(levels)
+    xd = _to_dev(x, torch.float32)
+    yd = None if y is None else _to_dev(y, torch.float32)
+    res = ops.modwt_lwcorr(xd, w.dec_lo, w.dec_hi, levels, y=yd, window=th, boundary=boundary, moments=True)
+    mom = _np(res["moments"], np.float64)
+    corr = np.full(mom[:, :, 0].shape, np.nan) if res["corr"] is None else _np(res["corr"], np.float64)
+    neff = local_n_eff(th, mom.shape[-1], len(w.dec_lo), levels, boundary)
+    z = NormalDist().inv_cdf(0.5 + 0.5 * ci_level)
+    names = [f"D_{j}" for j in range(1, levels + 1)]
+    out = []
+    with np.errstate(all="ignore"):
+        hw = np.where(neff > 3, z / np.sqrt(neff - 3), np.nan)
+        for m, c in zip(mom, corr):
+            zr = np.arctanh(c)
+            out.append(LocalWaveletCorrelation(names, m[:, 0], m[:, 1], m[:, 2], c,
+                                               np.stack((np.tanh(zr - hw), np.tanh(zr + hw)), -1), neff, len(th) - 1))
+    return out[0] if xd.dim() == 1 else out
+
+
+def local_wavelet_variance(x, levels: int, wavelet, half_width: int, window="uniform", boundary: str = "brickwall"):
+    """The time-localized wavelet variance of x per MODWT scale (``LocalWaveletCorrelation``'s
+    variance_x and n_eff; the pair fields are NaN): [n] in gives one result, [B, n] in a list."""
+    return local_wavelet_correlation(x, None, levels, wavelet, half_width, window, boundary)
+
+
 @dataclass
 class WaveletCorrelationMatrix:
     """Wavelet covariance and correlation matrices of M series per MODWT detail level and their
